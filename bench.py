@@ -11,8 +11,15 @@ torch.distributed with the gloo backend so that PyTorch never touches the GPU th
 Inputs are synthetic and resident in HBM before the timed region: hot-start links (seed 111), Gaussian source (seed 112),
 kappa = 0.141139, r = 1, BC = [1,1,1,-1].
 
-Rank 0 prints ONE JSON line.  Extra objects: "roofline" (Wilson Dslash kernel, algorithmic 960 B/site over HIP-event
-time measured on the library's own stream) and, at N = 1, "cpu_baseline" (the oracle timed on the host, a bounded sample).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`).
+--full adds what takes measurements of its own: "roofline" (Wilson Dslash kernel, algorithmic 960 B/site over HIP-event time
+measured on the library's own stream), the live PMC traffic, the secondary workloads, the N > 1 halo diagnostics and, at N = 1,
+"cpu_baseline" (the oracle timed on the host, a bounded sample) with the full-size parity checks.
+
+--dump-outputs DIR writes, after the timed steps, the solution vector x that the CG window left (what a caller of the solver
+receives; rank 0's sub-lattice at N > 1) as float64 .npy files: x_sample (real, imaginary parts of a fixed seeded sample of its
+complex entries, or all of them on small lattices), x_sample_index (their flat indices into x's (spin, t, z, y, x, colour)
+array) and x_norm2_per_timeslice (|x|^2 summed over each time slice of the whole field).
 """
 import argparse
 import json
@@ -48,6 +55,11 @@ def main():
     ap.add_argument("--set", action="append", default=[], help="library tunable key=value")
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 --pmc passes behind roofline.traffic")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: Dslash timing and roofline, PMC traffic, secondary workloads, "
+                         "N > 1 halo diagnostics, CPU baseline and full-size parity (--no-pmc, --no-cpu-baseline, --dslash-reps apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the CG window computed (the solution vector x) to DIR/<name>.npy")
     args = ap.parse_args()
     if args.pmc_child:
         return pmc_child(args)
@@ -170,17 +182,18 @@ def main():
         lq.bench_dslash(op or D, y, b, warm=n, reps=1)
 
     barrier()
-    settle()
-    ms_dslash = lq.bench_dslash(D, y, b, warm=20, reps=args.dslash_reps)              # mean over back-to-back launches
-    ms_median, _ = lq.bench_dslash_median(D, y, b, warm=5, reps=args.dslash_reps)       # per-launch events, median
-    barrier()
-    if dist is not None:
-        import torch
-        t = torch.tensor([ms_dslash], dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        ms_dslash = float(t.item())
-    dslash_gflops = WILSON_FLOP_PER_SITE * V / (ms_dslash * 1e-3) / 1e9
-    achieved = WILSON_BYTES_PER_SITE * Vloc / (ms_dslash * 1e-3) / 1e9     # GB/s per GPU, algorithmic bytes (960 B/site)
+    settle()                  # part of the warm-up of every run: the CG window below starts at steady clocks
+    if args.full:
+        ms_dslash = lq.bench_dslash(D, y, b, warm=20, reps=args.dslash_reps)              # mean over back-to-back launches
+        ms_median, _ = lq.bench_dslash_median(D, y, b, warm=5, reps=args.dslash_reps)       # per-launch events, median
+        barrier()
+        if dist is not None:
+            import torch
+            t = torch.tensor([ms_dslash], dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            ms_dslash = float(t.item())
+        dslash_gflops = WILSON_FLOP_PER_SITE * V / (ms_dslash * 1e-3) / 1e9
+        achieved = WILSON_BYTES_PER_SITE * Vloc / (ms_dslash * 1e-3) / 1e9     # GB/s per GPU, algorithmic bytes (960 B/site)
     recon_active = lat.get_param("recon_active")                            # 1: the kernel read 12 of the 18 reals of every link
     moved_per_site = 768 if recon_active else WILSON_BYTES_PER_SITE
 
@@ -192,20 +205,22 @@ def main():
     sess.iterate(args.steps)
     device_sync(); barrier()
     dt = time.perf_counter() - t0
-    sess.close()
+    sess.close()              # applies the pending deferred update of x: x is what the W + K iterations computed
     if dist is not None:
         import torch
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     iters_per_s = args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, x.download())      # before anything below reuses x
 
     # ---- roofline.traffic: HBM/fabric bytes of ONE launch of the dominant kernel, measured in THIS run: two separate rocprofv3
     # --pmc passes (FETCH_SIZE, WRITE_SIZE; kernel trace only) over a child process that applies the same operator to the same
     # synthetic configuration, corrected as MI355X_MICROARCH.md prescribes (FETCH_SIZE counts 64 B per 128-B request of a 16-B/lane
     # read on gfx950: doubled; both counters are KiB).  N = 1 only; null with a reason when rocprofv3 is unavailable.
     traffic, traffic18, traffic_source = None, None, "not measured (N > 1)"
-    if world == 1 and not force_dist:
+    if args.full and world == 1 and not force_dist:
         traffic, traffic18, traffic_source = (None, None, "skipped (--no-pmc)") if args.no_pmc else measure_traffic(args)
         settle()
 
@@ -229,40 +244,43 @@ def main():
                    "gauge_recon": lat.get_param("gauge_recon"), "gauge_recon_active": recon_active,
                    "comm_backend": lat.comm_backend, "comm_requested": args.comm, "comm_note": comm_note,
                    "ranks_share_device_0": bool(os.environ.get("LQCD_BENCH_SHARE_DEVICE"))},
-        "dslash_gflops": dslash_gflops,
-        "dslash_ms": ms_dslash,
-        "dslash_ms_median_per_launch_events": ms_median,
-        "roofline": {"bound": "hbm", "kernel": kernel_name(lat, recon_active) + " (mul!(y,D,x))", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                     "traffic_over_bytes_moved": (traffic / (moved_per_site * Vloc)) if traffic else None,
-                     "algorithmic_bytes_per_site": WILSON_BYTES_PER_SITE, "sites_per_launch": Vloc,
-                     # the default kernel rebuilds the third row of every (unitary) link: it MOVES 768 B/site for the 960 algorithmic ones
-                     "compulsory_bytes_moved_per_site": moved_per_site,
-                     "frac_by_bytes_moved": moved_per_site * Vloc / (ms_dslash * 1e-3) / 1e9 / HBM_PEAK_GBS},
     }
+    if args.full:
+        out.update({
+            "dslash_gflops": dslash_gflops,
+            "dslash_ms": ms_dslash,
+            "dslash_ms_median_per_launch_events": ms_median,
+            "roofline": {"bound": "hbm", "kernel": kernel_name(lat, recon_active) + " (mul!(y,D,x))", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                         "traffic_over_bytes_moved": (traffic / (moved_per_site * Vloc)) if traffic else None,
+                         "algorithmic_bytes_per_site": WILSON_BYTES_PER_SITE, "sites_per_launch": Vloc,
+                         # the default kernel rebuilds the third row of every (unitary) link: it MOVES 768 B/site for the 960 algorithmic ones
+                         "compulsory_bytes_moved_per_site": moved_per_site,
+                         "frac_by_bytes_moved": moved_per_site * Vloc / (ms_dslash * 1e-3) / 1e9 / HBM_PEAK_GBS},
+        })
 
-    # ---- the CG iteration's own roofline: what the fused iteration MOVES (the SURVEY 8(d) figure of 4224 B/site is the UNFUSED model -- 2 x 960 + 12 spinor
-    # passes -- and would read as ~1.0 x peak against ms_per_step; the fused iteration writes no q = D^+D p, updates r in D^+'s epilogue, x every second iteration,
-    # and reads 12 of the 18 reals of a link)
-    link_b = 384 if recon_active else 576
-    per_kernel_moved = {"D": 192 + link_b + 192, "Ddag_update_mode": 192 + link_b + 192 + 192, "cg_update_even": 3 * 192, "cg_update_odd": 6 * 192}
-    moved_iter = (per_kernel_moved["D"] + per_kernel_moved["Ddag_update_mode"] + 0.5 * (per_kernel_moved["cg_update_even"] + per_kernel_moved["cg_update_odd"])) * Vloc
-    t_iter = dt / args.steps
-    cg_traffic = None
-    if CG_TRAFFIC and all(CG_TRAFFIC.get(k) for k in per_kernel_moved):
-        cg_traffic = CG_TRAFFIC["D"] + CG_TRAFFIC["Ddag_update_mode"] + 0.5 * (CG_TRAFFIC["cg_update_even"] + CG_TRAFFIC["cg_update_odd"])
-    out["cg_roofline"] = {"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS,
-                          "bytes_moved_per_site_per_kernel": per_kernel_moved, "bytes_moved_per_iteration": moved_iter,
-                          "achieved": moved_iter / t_iter / 1e9, "frac": moved_iter / t_iter / 1e9 / HBM_PEAK_GBS,
-                          "traffic_per_kernel": dict(CG_TRAFFIC) if CG_TRAFFIC else None, "traffic": cg_traffic,
-                          "frac_by_traffic": (cg_traffic / t_iter / 1e9 / HBM_PEAK_GBS) if cg_traffic else None,
-                          "survey_unfused_model_bytes_per_site": 4224,
-                          "note": "frac = bytes the fused iteration must move / ms_per_step / peak; roofline.frac (Dslash) is on SURVEY 8(d)'s 960 algorithmic B/site "
-                                  "while the default kernel moves 768 (roofline.frac_by_bytes_moved)"}
-    out["roofline"]["note"] = "frac is on the 960-B/site algorithmic model of SURVEY 8(d); the default kernel rebuilds row 2 of every link and moves 768 B/site (frac_by_bytes_moved)"
+        # ---- the CG iteration's own roofline: what the fused iteration MOVES (the SURVEY 8(d) figure of 4224 B/site is the UNFUSED model -- 2 x 960 + 12 spinor
+        # passes -- and would read as ~1.0 x peak against ms_per_step; the fused iteration writes no q = D^+D p, updates r in D^+'s epilogue, x every second iteration,
+        # and reads 12 of the 18 reals of a link)
+        link_b = 384 if recon_active else 576
+        per_kernel_moved = {"D": 192 + link_b + 192, "Ddag_update_mode": 192 + link_b + 192 + 192, "cg_update_even": 3 * 192, "cg_update_odd": 6 * 192}
+        moved_iter = (per_kernel_moved["D"] + per_kernel_moved["Ddag_update_mode"] + 0.5 * (per_kernel_moved["cg_update_even"] + per_kernel_moved["cg_update_odd"])) * Vloc
+        t_iter = dt / args.steps
+        cg_traffic = None
+        if CG_TRAFFIC and all(CG_TRAFFIC.get(k) for k in per_kernel_moved):
+            cg_traffic = CG_TRAFFIC["D"] + CG_TRAFFIC["Ddag_update_mode"] + 0.5 * (CG_TRAFFIC["cg_update_even"] + CG_TRAFFIC["cg_update_odd"])
+        out["cg_roofline"] = {"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS,
+                              "bytes_moved_per_site_per_kernel": per_kernel_moved, "bytes_moved_per_iteration": moved_iter,
+                              "achieved": moved_iter / t_iter / 1e9, "frac": moved_iter / t_iter / 1e9 / HBM_PEAK_GBS,
+                              "traffic_per_kernel": dict(CG_TRAFFIC) if CG_TRAFFIC else None, "traffic": cg_traffic,
+                              "frac_by_traffic": (cg_traffic / t_iter / 1e9 / HBM_PEAK_GBS) if cg_traffic else None,
+                              "survey_unfused_model_bytes_per_site": 4224,
+                              "note": "frac = bytes the fused iteration must move / ms_per_step / peak; roofline.frac (Dslash) is on SURVEY 8(d)'s 960 algorithmic B/site "
+                                      "while the default kernel moves 768 (roofline.frac_by_bytes_moved)"}
+        out["roofline"]["note"] = "frac is on the 960-B/site algorithmic model of SURVEY 8(d); the default kernel rebuilds row 2 of every link and moves 768 B/site (frac_by_bytes_moved)"
 
     # ---- secondary, N > 1 (outside the timed region): where the time of a partitioned operator application goes on real links
-    if (world > 1 or force_dist) and any(p > 1 for p in pe) or (force_dist and os.environ.get("LQCD_FORCE_PARTITION")):
+    if args.full and ((world > 1 or force_dist) and any(p > 1 for p in pe) or (force_dist and os.environ.get("LQCD_FORCE_PARTITION"))):
         import ctypes as C
         import torch
         ph = (C.c_double * 6)()
@@ -295,7 +313,7 @@ def main():
 
     # ---- secondary (outside the timed region, not part of `value`): the same operator with all 18 stored reals of every link read
     # (gauge_recon = 18; what the default falls back to when a field is not unitary to 1e-14): 960 B/site moved.
-    if world == 1 and not force_dist:
+    if args.full and world == 1 and not force_dist:
       recon0 = lat.get_param("gauge_recon")
       try:
         lat.set_param("gauge_recon", 18)
@@ -316,7 +334,7 @@ def main():
 
     # ---- secondary (outside the timed region): links as the reference's own files hold them -- 11 significant digits, unitary to ~1e-10, so the 12-real gate
     # (1e-14) fails.  The scalar-addressing kernel then reads rows 0, 1 in fp64 + the fp32 deviation of row 2 ("12 + delta", 896 B/site moved, recon_active 2).
-    if world == 1 and not force_dist:
+    if args.full and world == 1 and not force_dist:
       try:
         import numpy as _np
         Uh = U.download()
@@ -339,7 +357,7 @@ def main():
         out["reference_format_links"] = {"error": str(e)}
 
     # ---- secondary (outside the timed region, not part of `value`): time to solution r.r < 1e-16, fp64 CG vs mixed-precision CG
-    if world == 1 and not force_dist:
+    if args.full and world == 1 and not force_dist:
       try:
         D.eps_CG = 1e-16
         A = lq.DdagD_operator(D)
@@ -360,7 +378,7 @@ def main():
     # ---- secondary (outside the timed region): the same CG window on links that went through molecular dynamics -- a copy of the field, 20 MD
     # steps of the reference's Sexton-Weingarten gauge legs (standardMD.jl:146-166, N = 10, dtau = 0.05: 400 link updates from a Gaussian
     # momentum), which is where the 12-real criterion (unitary to 1e-14) would be lost without the projection inside the link update
-    if world == 1 and not force_dist:
+    if args.full and world == 1 and not force_dist:
       try:
         U2, p2 = lq.Gaugefields(lat), lq.Gaugefields(lat)
         lq.substitute_U_(U2, U)
@@ -384,7 +402,7 @@ def main():
     # ---- secondary (outside the timed region): ONE molecular-dynamics step of the 2-flavour Wilson HMC on this lattice, measured end to end with everything resident --
     # the reference's runMD_QPQ_sw! (standardMD.jl:146-166, Sexton-Weingarten N = 10: 10 momentum updates, 20 link half steps, one P_update_fermion! = calc_UdSfdU! with
     # eps_CG 1e-16 + Traceless_antihermitian_add!) on a copy of the links, steps of 1e-9 so that the configuration stays where it is; fp64 and with the fp32 inner chain
-    if world == 1 and not force_dist:
+    if args.full and world == 1 and not force_dist:
       try:
         U3, p3, G3 = lq.Gaugefields(lat), lq.Gaugefields(lat), lq.Gaugefields(lat)
         lq.substitute_U_(U3, U)
@@ -418,7 +436,7 @@ def main():
       except Exception as e:
         out["md_step_wilson_hmc"] = {"error": str(e)}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(lq, U, b, gL)
         # max |HIP - oracle| / max |oracle| of D b (default and 18-real kernel instances) and D^+ b on the bench lattice itself
         out["fullsize_dslash_rel_err"] = out["cpu_baseline"].pop("fullsize_dslash_rel_err", None)
@@ -441,6 +459,25 @@ def _flush_c_stdio():
         ctypes.CDLL(None).fflush(None)
     except Exception:
         pass
+
+
+DUMP_SAMPLE = 1 << 21          # complex entries of x written at most: 32 MB of values + 16 MB of indices
+DUMP_SEED = 20260611
+
+
+def dump_outputs(d, xh):
+    """--dump-outputs: the CG solution x (complex128, (spin, t, z, y, x, colour)) as float64 .npy files under d -- a fixed seeded sample of
+    its entries (all of them when there are at most DUMP_SAMPLE), their flat indices, and |x|^2 per time slice of the whole field."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    flat = xh.reshape(-1)
+    if flat.size <= DUMP_SAMPLE:
+        idx = np.arange(flat.size)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.size, DUMP_SAMPLE, replace=False))
+    np.save(os.path.join(d, "x_sample.npy"), np.stack([flat[idx].real, flat[idx].imag], axis=1).astype(np.float64))
+    np.save(os.path.join(d, "x_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, "x_norm2_per_timeslice.npy"), (np.abs(xh) ** 2).sum(axis=(0, 2, 3, 4, 5)).astype(np.float64))
 
 
 def pmc_child(args):

@@ -56,7 +56,7 @@ case $stage in
     python scripts/delta_probe.py 2>&1 | tail -5 | tee $out/delta.log
     python scripts/delta_probe.py --L 16,16,16,32 --dev 1e-9 2>&1 | tail -4 | tee -a $out/delta.log
     timeout 600 python -m pytest tests/test_gpu_recon12.py tests/test_gpu_pipe.py tests/test_golden_io.py tests/test_gpu_parity.py -q -x 2>&1 | tail -8 | tee $out/pytest.log
-    timeout 600 python bench.py --no-pmc > $out/bench.json 2> $out/bench.err; python -c "import json; d=json.load(open('$out/bench.json')); print(d['value'], d['roofline']['frac'], d['gauge_recon18_all_reals_read'], d['reference_format_links'])"
+    timeout 600 python bench.py --full --no-pmc > $out/bench.json 2> $out/bench.err; python -c "import json; d=json.load(open('$out/bench.json')); print(d['value'], d['roofline']['frac'], d['gauge_recon18_all_reals_read'], d['reference_format_links'])"
     ;;
   mixedeo)    # mixed-precision even-odd BiCGStab
     timeout 900 python -m pytest tests/test_gpu_mixed.py tests/test_gpu_md_mixed.py tests/test_gpu_pair32.py -q -x 2>&1 | tail -12 | tee $out/pytest.log
@@ -67,7 +67,7 @@ case $stage in
         tests/test_gpu_reunit.py tests/test_gpu_hmc_partitioned.py tests/test_gpu_lifecycle.py tests/test_gpu_clover.py tests/test_gpu_domainwall.py -q -x --durations=5 2>&1 | tail -14 | tee $out/pytest.log
     timeout 300 python -m pytest tests/test_gpu_parity.py -q -x -k "c_abi" 2>&1 | tail -3 | tee -a $out/pytest.log
     timeout 900 python scripts/bench_configs.py > $out/bench_configs.log 2> $out/bench_configs.err; sed -n 5p $out/bench_configs.log | cut -c1-900; tail -3 $out/bench_configs.err
-    timeout 600 python bench.py > $out/bench.json 2> $out/bench.err; python -c "import json; d=json.load(open('$out/bench.json')); print(d['value'], d['dslash_ms'], d['roofline']['frac'], d['gauge_recon18_all_reals_read']['dslash_ms'], d['reference_format_links'])"; tail -2 $out/bench.err
+    timeout 600 python bench.py --full > $out/bench.json 2> $out/bench.err; python -c "import json; d=json.load(open('$out/bench.json')); print(d['value'], d['dslash_ms'], d['roofline']['frac'], d['gauge_recon18_all_reals_read']['dslash_ms'], d['reference_format_links'])"; tail -2 $out/bench.err
     ;;
   pu)         # momentum + link update as one sweep vs two passes
     timeout 600 python -m pytest tests/test_gpu_md.py tests/test_gpu_reunit.py tests/test_gpu_reference_callers.py tests/test_gpu_stout.py -q -x 2>&1 | tail -3
@@ -186,7 +186,7 @@ PY
     python scripts/timeline.py "$t" cg_update_odd 2>&1 | tee -a $out/timeline.log
     rm -rf $out/trace1
     timeout 900 python bench.py --steps 20 --warmup 5 > $out/bench_n1.json 2> $out/bench_n1.err; tail -c 3000 $out/bench_n1.json; tail -3 $out/bench_n1.err
-    LQCD_BENCH_FORCE_DIST=1 LQCD_FORCE_PARTITION=14 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 600 python bench.py --lattice 32,16,16,32 --no-cpu-baseline --no-pmc > $out/bench_proxy_n8local.json 2> $out/bench_proxy.err; python -c "
+    LQCD_BENCH_FORCE_DIST=1 LQCD_FORCE_PARTITION=14 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 600 python bench.py --full --lattice 32,16,16,32 --no-cpu-baseline --no-pmc > $out/bench_proxy_n8local.json 2> $out/bench_proxy.err; python -c "
 import json; d=json.load(open('$out/bench_proxy_n8local.json')); print({k: d.get(k) for k in ('value','ms_per_step','halo_phases_ms_max_over_ranks','halo_stream_mode_rank0','allreduce_latency_us')})"; tail -3 $out/bench_proxy.err
     ;;
   call3)      # round 5, call 3: where did the suite stall (per-test timeout with stack dump), the ring of search-direction buffers (cg_defer_x = K), proxy with it

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -17,7 +18,7 @@ def test_bench_distributed_control_path_on_a_self_partitioned_lattice(mask):
     env = dict(os.environ, LQCD_BENCH_FORCE_DIST="1", LQCD_FORCE_PARTITION=mask, HSA_ENABLE_IPC_MODE_LEGACY="0",
                MASTER_ADDR="127.0.0.1", MASTER_PORT="29611", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "5", "--lattice", "16,16,16,32",
-                        "--dslash-reps", "50", "--no-cpu-baseline", "--no-pmc"], capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
+                        "--dslash-reps", "50", "--no-cpu-baseline", "--no-pmc", "--full"], capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
@@ -41,7 +42,7 @@ def test_bench_with_real_processes_on_one_gpu(nproc, lattice, comm):
     port = str(29660 + nproc)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=%d" % nproc, "--master-addr", "127.0.0.1", "--master-port", port,
                         os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "40", "--warmup", "5", "--lattice", lattice, "--dslash-reps", "50",
-                        "--comm", comm], capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
+                        "--comm", comm, "--full"], capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, lines
@@ -54,3 +55,33 @@ def test_bench_with_real_processes_on_one_gpu(nproc, lattice, comm):
     ph = d["halo_phases_ms_max_over_ranks"]
     assert all(ph[k] is not None and ph[k] >= 0 for k in ("pack", "interior", "total_synchronised")), ph
     assert d["allreduce_latency_us"] > 0 and d["halo_stream_mode_rank0"]["chosen"] in (0, 1, 2, 3, 4)
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """The plain N = 1 line (no --full) holds the headline only, --steps sets the timed window, and --dump-outputs writes the CG solution as
+    float64 .npy files (within 64 MB) that two runs with the same arguments reproduce."""
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("dump%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "4", "--lattice", "16,16,16,32",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, lines
+        out = json.loads(lines[0])
+        assert out["steps"] == 30 and out["warmup"] == 4 and out["unit"] == "iter/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+        assert out["value"] > 0 and abs(out["ms_per_step"] * out["value"] - 1e3) < 1e-6 * 1e3
+        assert not {"roofline", "cg_roofline", "dslash_ms", "cpu_baseline", "gauge_recon18_all_reals_read", "md_step_wilson_hmc"} & set(out)
+        files = sorted(os.listdir(str(d)))
+        assert files == ["x_norm2_per_timeslice.npy", "x_sample.npy", "x_sample_index.npy"], files
+        arrs = {f: np.load(str(d / f)) for f in files}
+        assert all(a.dtype == np.float64 for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        n = 4 * 32 * 16 * 16 * 16 * 3                    # every entry of x on this lattice
+        assert arrs["x_sample.npy"].shape == (n, 2) and np.array_equal(arrs["x_sample_index.npy"], np.arange(n, dtype=np.float64))
+        xs = arrs["x_sample.npy"]
+        norm2 = arrs["x_norm2_per_timeslice.npy"]
+        assert norm2.shape == (32,) and np.all(np.isfinite(xs)) and np.all(norm2 > 0)
+        assert abs(norm2.sum() - float((xs ** 2).sum())) <= 1e-12 * norm2.sum()
+        runs.append(arrs)
+    for f in runs[0]:
+        np.testing.assert_allclose(runs[1][f], runs[0][f], rtol=1e-12, atol=0)

@@ -145,7 +145,7 @@ def test_bench_control_path_two_processes(lq, tmp_path):
         env.pop("LQCD_BENCH_FORCE_DIST", None)
         port = str(29617 + k)
         r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-                            "--master-port", port, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2"] + flags,
+                            "--master-port", port, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full"] + flags,
                            capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
         assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
         lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -168,6 +168,27 @@ def test_bench_control_path_two_processes(lq, tmp_path):
             pr = [open(os.path.join(str(d), "rank%d.peer" % q), "rb").read() for q in (0, 1)]      # written once the gathered blobs were in rank order
             assert b"pe=1,1,1,2 nranks=2 device=0" in pr[0] and b"device=1" in pr[1]
             assert not os.path.exists(os.path.join(str(d), "rank0.id"))
+
+
+def test_bench_plain_line_two_processes(lq, tmp_path):
+    """Without --full the N > 1 line holds the headline and the run's configuration only: no Dslash timing, halo or all-reduce diagnostics."""
+    import json
+    stub_dir = os.path.join(ROOT, "tests", "stub")
+    r = subprocess.run(["make", "-s", "-C", stub_dir], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    env = dict(os.environ, LQCD_HIP_LIB=os.path.join(stub_dir, "liblqcd_stub.so"), LQCD_STUB_REAL_LIB=lq.lib.SO_PATH, LQCD_STUB_DIR=str(tmp_path))
+    env.pop("LQCD_BENCH_FORCE_DIST", None)
+    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
+                        "--master-port", "29623", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "7", "--warmup", "2"],
+                       capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    out = json.loads(lines[-1])
+    assert sum(1 for ln in lines if ln.startswith("{")) == 1
+    assert out["n_gpus"] == 2 and out["steps"] == 7 and out["warmup"] == 2 and out["unit"] == "iter/s" and out["dtype"] == "f64"
+    assert out["value"] > 0 and abs(out["ms_per_step"] * out["value"] - 1e3) < 1e-9 * 1e3
+    assert out["config"]["pe_grid"] == [1, 1, 1, 2] and out["config"]["comm_backend"] == "peer"
+    assert not {"dslash_ms", "roofline", "cg_roofline", "halo_phases_ms_max_over_ranks", "allreduce_latency_us", "cpu_baseline"} & set(out)
 
 
 # ------------------------------------------------------------------ the Julia binding against the header (no Julia in the image)
