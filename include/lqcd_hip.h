@@ -394,6 +394,24 @@ int lqcd_link_staple(lqcd_gauge_t out, int mu_out, lqcd_gauge_t U, int mu, doubl
 int lqcd_link_exp_mul(lqcd_gauge_t W, int mu_w, double t, lqcd_gauge_t P, int mu_p, lqcd_gauge_t U, int mu_u);
 int lqcd_link_add_ta_staple(lqcd_gauge_t P, int mu_p, double factor, lqcd_gauge_t U, int mu, double beta);
 
+/* ---------------------------------------------------------------- gradient flow and the observables along it (src/system/lqcd.jl:95-100,149-164)
+ * Wilson flow dV/dt = Z V, Z = TA of the staple force of lqcd_gauge_force at beta = 6 (one Euler step = one stout step with rho = eps), integrated with
+ * Luscher's third-order Runge-Kutta scheme (JHEP 08 (2010) 071).  Directions 0..3 = x, y, z, t; TA(M) = (M - M^+)/2 - tr(M - M^+)/6.
+ * Field strength from n closed loops through x in the (mu, nu) plane: G = TA(sum)/n, sets "plaquette" (1 leaf), "clover" (4 leaves), "rect" (the eight
+ * 1x2 / 2x1 rectangles with a corner at x).  Observables, in order:
+ *   p (as lqcd_gauge_plaquette), E_plaq = 2 sum_{mu<nu} Re tr(1 - P) per site = 36 (1 - p), E_clov = -1/2 sum_{mu,nu} tr G G per site (clover),
+ *   Q_plaq, Q_clov = -1/(32 pi^2) sum_x eps_{mu nu rho sigma} tr G_{mu nu} G_{rho sigma} (eps_xyzt = +1) of the plaquette / clover set,
+ *   Q_impr = 5/3 Q_clov - 1/12 Q_rect with Q_rect = 2 Q[rect].
+ * Collective on a partitioned lattice (RCCL or the peer backend, as lqcd_gauge_force); every rank gets the same values.  There the observables read a
+ * depth-1 halo-extended block of links (corners included): the rectangles need depth 2, so Q_impr is NaN on a partitioned lattice.  The flow writes V in
+ * place (its version changes, so every cached copy of the links is rebuilt); the accumulator and the other temporaries belong to the context. */
+#define LQCD_FLOW_NOBS 6
+int lqcd_gradient_flow(lqcd_gauge_t V, double eps, int nsteps);                  /* flow!(Usmr, gradientflow) (lqcd.jl:99,153) with Nflow = nsteps */
+int lqcd_gauge_flow_observables(lqcd_gauge_t V, double obs[LQCD_FLOW_NOBS]);     /* Energy_density / Topological_charge (lqcd.jl:155-162): p, E_plaq, E_clov, Q_plaq, Q_clov, Q_impr */
+/* the driver's gradient-flow schedule (lqcd.jl:149-164) resident on the device: nsteps steps of size eps, the observables after every `every`-th step;
+ * table receives nsteps/every rows [t, p, E_plaq, E_clov, Q_plaq, Q_clov, Q_impr] (row-major).  One device-to-host copy, at the end */
+int lqcd_gradient_flow_measure(lqcd_gauge_t V, double eps, int nsteps, int every, double* table);
+
 /* the SURVEY.md 8(d) protocol: every application between its own HIP events, median and mean over reps */
 int lqcd_bench_dslash_median(lqcd_op_t op, lqcd_spinor_t out, lqcd_spinor_t in, int dagger, int warm, int reps, double* median_ms,
                              double* mean_ms);

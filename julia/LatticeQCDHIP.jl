@@ -32,13 +32,14 @@ import Base: similar, adjoint
 import Gaugefields: AbstractGaugefields, GaugeAction, Initialize_Gaugefields, substitute_U!, exptU!, Traceless_antihermitian_add!, calc_dSdUμ!,
     evaluate_GaugeAction, initialize_TA_Gaugefields, gauss_distribution!, calc_smearedU, println_verbose_level1,
     println_verbose_level2, println_verbose_level3, get_myrank, calculate_Plaquette, calculate_Polyakov_loop, load_BridgeText!, load_gaugefield!,
-    CovNeuralnet, CovLayer, STOUT_Layer, back_prop
+    CovNeuralnet, CovLayer, STOUT_Layer, back_prop, Gradientflow, flow!
 import LatticeDiracOperators: Dirac_operator, DdagD_operator, FermiAction, Initialize_pseudofermion_fields,
     gauss_sampling_in_action!, sample_pseudofermions!, evaluate_FermiAction, calc_UdSfdU!, solve_DinvX!, shiftedcg,
     clear_fermion!, substitute_fermion!, add_fermion!, gauss_distribution_fermion!, Z4_distribution_fermi!,
     AbstractFermionfields_4D
 
-export Initialize_HIPGaugefields, HIPLattice, HIPLink, HIPTALink, HIPFermion, HIPDirac, HIPFermiAction, reunitarize!, activate!, deactivate!
+export Initialize_HIPGaugefields, HIPLattice, HIPLink, HIPTALink, HIPFermion, HIPDirac, HIPFermiAction, reunitarize!, activate!, deactivate!,
+    HIPGradientflow, flow_observables, energy_density, topological_charge, gradient_flow_measure
 
 const LIB = get(ENV, "LQCD_HIP_LIB", joinpath(@__DIR__, "..", "latticeqcd.jl_amd", "csrc", "liblqcd_hip.so"))
 
@@ -305,6 +306,53 @@ function calculate_Polyakov_loop(U::Vector{HIPLink}, temps...)
     return complex(re[], im_[])
 end
 reunitarize!(U::Vector{HIPLink}) = check(ccall((:lqcd_gauge_reunitarize, LIB), Cint, (Ptr{Cvoid},), whole(U).h))
+
+# the driver's gradient-flow block (lqcd.jl:95-100,149-164), which imports Gradientflow and flow! from Gaugefields (lqcd.jl:6-10): the methods below
+# extend those generics, so `Gradientflow(univ.U, Nflow = 1, eps = eps_flow)` (:99) and `flow!(Usmr, gradientflow)` (:153) resolve on the binding's
+# links.  `Usmr = deepcopy(univ.U)` (:150) copies the device field (Base.deepcopy_internal below), so the flow leaves univ.U alone.  The observables
+# measured along the flow (Energy_density / Topological_charge); field order of lqcd_gauge_flow_observables: p, E_plaq, E_clov, Q_plaq, Q_clov, Q_impr
+struct HIPGradientflow
+    Nflow::Int
+    eps::Float64
+end
+Gradientflow(U::Vector{HIPLink}; Nflow = 1, eps = 0.01) = HIPGradientflow(Nflow, eps)
+function flow!(U::Vector{HIPLink}, gf::HIPGradientflow)
+    check(ccall((:lqcd_gradient_flow, LIB), Cint, (Ptr{Cvoid}, Float64, Cint), whole(U).h, gf.eps, gf.Nflow))
+    return U
+end
+# deepcopy(U): a new device field with the same links (the default deepcopy would copy the handles, and the flow would write the original)
+function Base.deepcopy_internal(U::Vector{HIPLink}, stackdict::IdDict)
+    haskey(stackdict, U) && return stackdict[U]
+    V = similar(U)
+    substitute_U!(V, U)
+    stackdict[U] = V
+    return V
+end
+function flow_observables(U::Vector{HIPLink})
+    obs = zeros(Float64, 6)
+    check(ccall((:lqcd_gauge_flow_observables, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), whole(U).h, obs))
+    return (p = obs[1], E_plaq = obs[2], E_clov = obs[3], Q_plaq = obs[4], Q_clov = obs[5], Q_impr = obs[6])
+end
+function energy_density(U::Vector{HIPLink}; kind = "clover")
+    o = flow_observables(U)
+    kind == "plaquette" && return o.E_plaq
+    kind == "clover" && return o.E_clov
+    error("energy_density: kind $kind (plaquette | clover)")
+end
+function topological_charge(U::Vector{HIPLink}; kind = "clover")
+    o = flow_observables(U)
+    kind == "plaquette" && return o.Q_plaq
+    kind == "clover" && return o.Q_clov
+    kind == "improved" && return o.Q_impr    # NaN on a partitioned lattice (the rectangles need a depth-2 halo)
+    error("topological_charge: kind $kind (plaquette | clover | improved)")
+end
+# the whole flow schedule resident on the device: numflow steps, the observables after every `every`-th; rows [t, p, E_plaq, E_clov, Q_plaq, Q_clov, Q_impr]
+function gradient_flow_measure(U::Vector{HIPLink}, eps::Real, numflow::Integer, every::Integer)
+    nrows = numflow ÷ every
+    tab = zeros(Float64, 7, nrows)       # column-major 7 x nrows = the C side's row-major nrows x 7
+    check(ccall((:lqcd_gradient_flow_measure, LIB), Cint, (Ptr{Cvoid}, Float64, Cint, Cint, Ptr{Float64}), whole(U).h, Float64(eps), numflow, every, tab))
+    return [tab[j, i] for i = 1:nrows, j = 1:7]
+end
 
 # substitute_U!(Uold, U) / substitute_U!(U, Uold) (standardHMC.jl:45,84) and substitute_U!(U[mu], W) (AbstractMD.jl:93)
 function substitute_U!(dst::Vector{HIPLink}, src::Vector{HIPLink})

@@ -579,6 +579,7 @@ __device__ __forceinline__ void horner(cd (&T)[9], const cd (&R)[9], const cd (&
 struct ExtGeom {
     int L[4], E[4];
     size_t n;          // E0 E1 E2 E3
+    int nm;            // matrices per site in the block: 10 (links + Lambda planes), 4 (links only: the gradient-flow observables)
 };
 __host__ __device__ inline size_t ext_site(const ExtGeom& eg, const int (&c)[4]) {      // c = local coordinates in [-1, L]
     return (size_t)(c[0] + 1) + (size_t)eg.E[0] * ((size_t)(c[1] + 1) + (size_t)eg.E[1] * ((size_t)(c[2] + 1) + (size_t)eg.E[2] * (size_t)(c[3] + 1)));
@@ -591,7 +592,7 @@ __global__ __launch_bounds__(64) void clover_ext_fill_kernel(Geom g, ExtGeom eg,
     cb_to_coords(g, p, i, c);
     const size_t e = ext_site(eg, c);
     const int Gs = glink_stride(g);
-    for (int m = 0; m < 10; m++) {
+    for (int m = 0; m < eg.nm; m++) {
         const double2* src = m < 4 ? U + glink_off(g, p, m, i) : lam + lambda_off(g, p, i, m - 4);
         const int st_ = m < 4 ? Gs : 64;
 #pragma unroll
@@ -616,8 +617,9 @@ __global__ __launch_bounds__(256) void clover_ext_face_kernel(ExtGeom eg, int d,
     if (f >= F) return;
     const int layer = pack ? (side ? eg.L[d] : 1) : (side ? eg.L[d] + 1 : 0);
     const size_t e = ext_face_site(eg, d, f, layer);
-    double2* b = buf + (size_t)side * 90 * F + f;
-    for (int j = 0; j < 90; j++) {
+    const int nj = 9 * eg.nm;
+    double2* b = buf + (size_t)side * nj * F + f;
+    for (int j = 0; j < nj; j++) {
         if (pack) st(b + (size_t)j * F, ld(ext + (size_t)j * eg.n + e));
         else st(ext + (size_t)j * eg.n + e, ld(b + (size_t)j * F));
     }
@@ -740,13 +742,15 @@ static int sigma_table(SigmaTab& tb) {
     return LQCD_OK;
 }
 
-// halo-extended copy of the links and the Lambda matrices (partitioned lattice)
-static int clover_ext_build(lqcd_ctx_s* c, const lqcd_gauge_s* U, const double2* lam, ExtGeom& eg) {
+// halo-extended copy of the links and the Lambda matrices (partitioned lattice); nm = 4: the links alone (lam is not read)
+static int clover_ext_build(lqcd_ctx_s* c, const lqcd_gauge_s* U, const double2* lam, ExtGeom& eg, int nm = 10) {
     for (int k = 0; k < 4; k++) { eg.L[k] = c->geom.L[k]; eg.E[k] = c->geom.L[k] + 2; }
     eg.n = (size_t)eg.E[0] * eg.E[1] * eg.E[2] * eg.E[3];
+    eg.nm = nm;
+    const size_t P = 9 * (size_t)nm;     // planes of the block
     size_t Fmax = 0;
     for (int d = 0; d < 4; d++) Fmax = std::max(Fmax, eg.n / (size_t)eg.E[d]);
-    const size_t ext_bytes = 90 * eg.n * sizeof(double2), buf_bytes = 2 * 90 * Fmax * sizeof(double2);
+    const size_t ext_bytes = P * eg.n * sizeof(double2), buf_bytes = 2 * P * Fmax * sizeof(double2);
     if (c->clover_ext_bytes < ext_bytes) {
         (void)hipFree(c->clover_ext);
         c->clover_ext = nullptr; c->clover_ext_bytes = 0;
@@ -773,15 +777,15 @@ static int clover_ext_build(lqcd_ctx_s* c, const lqcd_gauge_s* U, const double2*
         if (c->geom.part[d]) {
             // my lower boundary layer (side 0) is the -d neighbour's upper halo (side 1), my upper layer its +d neighbour's lower halo
             ARGCHK(c->has_comm, "clover force: communicator not initialised (call lqcd_ctx_comm_init or lqcd_ctx_peer_init)");
-            const size_t nb = 90 * F * sizeof(double2);     // bytes per side
-            const CommXfer x[2] = {{sendb, recvb + 90 * F, nb, d, 1},            // my lower layer travels backward; their lower layer -> my upper halo
-                                   {sendb + 90 * F, recvb, nb, d, 0}};           // my upper layer travels forward; their upper layer -> my lower halo
+            const size_t nb = P * F * sizeof(double2);     // bytes per side
+            const CommXfer x[2] = {{sendb, recvb + P * F, nb, d, 1},             // my lower layer travels backward; their lower layer -> my upper halo
+                                   {sendb + P * F, recvb, nb, d, 0}};            // my upper layer travels forward; their upper layer -> my lower halo
             LQCHK(comm_sendrecv(c, x, 2, c->stream, false));
             src = recvb;
         } else {
             // periodic wrap on this rank: lower halo <- own upper layer, upper halo <- own lower layer
-            HIPCHK(hipMemcpyAsync(recvb, sendb + 90 * F, 90 * F * sizeof(double2), hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(recvb + 90 * F, sendb, 90 * F * sizeof(double2), hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(recvb, sendb + P * F, P * F * sizeof(double2), hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(recvb + P * F, sendb, P * F * sizeof(double2), hipMemcpyDeviceToDevice, c->stream));
             src = recvb;
         }
         hipLaunchKernelGGL(clover_ext_face_kernel, grid, dim3(256), 0, c->stream, eg, d, F, ext, src, 0);
@@ -884,6 +888,17 @@ double2* stout_lambda_buffer(lqcd_ctx_s* c) {
     if (!c->clover_q[0] && hipMalloc((void**)&c->clover_q[0], clover_lambda_elems(c->geom) * sizeof(double2)) != hipSuccess) return nullptr;
     (void)hipMemsetAsync(c->clover_q[0], 0, clover_lambda_elems(c->geom) * sizeof(double2), c->stream);      // planes 4, 5 travel with the faces: keep them finite
     return c->clover_q[0];
+}
+
+// the halo-extended block of the links alone (gradient-flow observables, flow.hip): four matrices per site, no Lambda planes.  *ext = the block (link mu
+// of local site c at ext[mu][9][n], c in [-1, L]) and its extents E; collective on RCCL / peer ranks
+int gauge_ext_links(lqcd_ctx_s* c, const lqcd_gauge_s* U, const double2** ext, int E[4], size_t* n) {
+    ExtGeom eg;
+    LQCHK(clover_ext_build(c, U, nullptr, eg, 4));
+    for (int k = 0; k < 4; k++) E[k] = eg.E[k];
+    *n = eg.n;
+    *ext = c->clover_ext;
+    return LQCD_OK;
 }
 
 // out = (accumulate ? out : 0) + scale * (clover part of "U dS_f/dU"); lam = scratch of clover_lambda_elems() elements

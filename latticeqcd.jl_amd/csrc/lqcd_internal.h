@@ -792,6 +792,11 @@ struct lqcd_ctx_s {
     double2* gf_ghost[4] = {}, *gf_gsend[4] = {}, *gf_wsend[4] = {}, *gf_wrecv[4] = {};
     lqcd_gauge_s* stout_tmp[2] = {};    // W = U A and the N matrices of the stout back-propagation (md.hip), created on first use
     double2* gauge_spare = nullptr;     // second link buffer of the fused momentum + link update (md.hip staple_force_expu), allocated on first use
+    double2* flow_x = nullptr;          // gradient flow (flow.hip): the RK3 accumulator, gauge-shaped, allocated on first use
+    double* flow_partial = nullptr;     // ... block partials of the flow observables
+    size_t flow_partial_n = 0;
+    double* flow_tab = nullptr;         // ... device table of raw observables (+ the projection flag), grown on demand
+    size_t flow_tab_n = 0;
     double2* clover_q[2] = {};          // clover sums / transport ping-pong, six 3x3 matrices per site (clover.hip)
     double2* clover_ext = nullptr;      // halo-extended links + Lambda matrices of the partitioned clover force, and its face buffers
     size_t clover_ext_bytes = 0;

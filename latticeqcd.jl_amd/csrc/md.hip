@@ -196,6 +196,9 @@ struct GFArgs {
     double dt;
     unsigned* notproj;
     int reunit;
+    // FLOW instances (one RK3 stage of the gradient flow, flow.hip): the accumulator X in `out` becomes xscale X + factor TA(G) -- xread = 0 (stage 1): X is not read
+    double xscale;
+    int xread;
 };
 
 // U_nu at the site c + dir_hat: local, or from the forward ghost slice when the step leaves the rank
@@ -233,9 +236,9 @@ __device__ __forceinline__ void lower_staple_at(cd (&w)[9], const GFArgs& k, con
 // fully templated body below needs > 256 registers (1000+ spilled); this form holds them in 256 without scratch.
 template <int MODE>
 __global__ __launch_bounds__(256) void gauge_force_kernel_part(GFArgs k) {
-    constexpr bool FUSE_TA = MODE == 1 || MODE == 3;
+    constexpr bool FUSE_TA = MODE == 1 || MODE == 3 || MODE == 4;      // MODE 4: the RK3 stage of the gradient flow, X <- xscale X + factor TA(G)
     const Geom& g = k.g;
-    const int p = blockIdx.x & 1, i = (blockIdx.x >> 1) * 64 + (threadIdx.x & 63), mu = MODE >= 2 ? k.mu_only : (int)(threadIdx.x >> 6);
+    const int p = blockIdx.x & 1, i = (blockIdx.x >> 1) * 64 + (threadIdx.x & 63), mu = (MODE == 2 || MODE == 3) ? k.mu_only : (int)(threadIdx.x >> 6);
     if (i >= g.Vh) return;
     const int Gs = glink_stride(g);
     int c[4];
@@ -289,6 +292,18 @@ __global__ __launch_bounds__(256) void gauge_force_kernel_part(GFArgs k) {
             for (int y = 0; y < 3; y++) a[x * 3 + y] = mk(f * (r[x * 3 + y].re - r[y * 3 + x].re), f * (r[x * 3 + y].im + r[y * 3 + x].im));
         const double tr = (a[0].im + a[4].im + a[8].im) / 3.0;
         a[0].im -= tr; a[4].im -= tr; a[8].im -= tr;
+        if constexpr (MODE == 4) {
+            if (k.xread) {
+#pragma unroll
+                for (int e = 0; e < 9; e++) {
+                    const cd pv = ld(o + (size_t)e * Gs);
+                    a[e] = mk(fma(k.xscale, pv.re, a[e].re), fma(k.xscale, pv.im, a[e].im));
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 9; e++) st(o + (size_t)e * Gs, a[e]);
+            return;
+        }
 #pragma unroll
         for (int e = 0; e < 9; e++) {
             const cd pv = ld(o + (size_t)e * Gs);
@@ -488,7 +503,7 @@ __device__ __forceinline__ void staple_plane_tile(cd (&A)[9], const GFArgs& k, i
     }
 }
 
-template <int MODE, int MU, bool PART, bool R2, bool EXPU = false, bool TILE = false>
+template <int MODE, int MU, bool PART, bool R2, bool EXPU = false, bool TILE = false, bool FLOW = false>
 __device__ __forceinline__ void staple_links(const GFArgs& k, int p, int i, int lane, const double2 (*own)[9][64], const double2 (*own2)[4][LQCD_STAPLE_TILE_ROWS][64] = nullptr) {
     constexpr bool FUSE_TA = MODE == 1 || MODE == 3;
     const Geom& g = k.g;
@@ -544,8 +559,15 @@ __device__ __forceinline__ void staple_links(const GFArgs& k, int p, int i, int 
         // triangle is read, the lower one follows -- bit for bit what the nine sums gave -- and 48 of the 144 bytes per link stay unread (profiles/r06_pmc_staple.log)
         auto addp = [&](auto E) {
             constexpr int e = decltype(E)::value;
-            const cd pv = EXPU ? ld_stream(o + (size_t)e * Gs) : ld(o + (size_t)e * Gs);
-            a[e] = mk(pv.re + a[e].re, pv.im + a[e].im);
+            if constexpr (FLOW) {      // gradient-flow stage: X <- xscale X + factor TA(G); stage 1 (xread = 0) does not read X
+                if (k.xread) {
+                    const cd pv = ld_stream(o + (size_t)e * Gs);
+                    a[e] = mk(fma(k.xscale, pv.re, a[e].re), fma(k.xscale, pv.im, a[e].im));
+                }
+            } else {
+                const cd pv = EXPU ? ld_stream(o + (size_t)e * Gs) : ld(o + (size_t)e * Gs);
+                a[e] = mk(pv.re + a[e].re, pv.im + a[e].im);
+            }
         };
         addp(std::integral_constant<int, 0>()); addp(std::integral_constant<int, 1>()); addp(std::integral_constant<int, 2>());
         addp(std::integral_constant<int, 4>()); addp(std::integral_constant<int, 5>()); addp(std::integral_constant<int, 8>());
@@ -577,7 +599,7 @@ __device__ __forceinline__ void staple_links(const GFArgs& k, int p, int i, int 
 #ifndef LQCD_STAPLE_OCC
 #define LQCD_STAPLE_OCC 2
 #endif
-template <int MODE, bool PART, bool R2 = false, bool EXPU = false>
+template <int MODE, bool PART, bool R2 = false, bool EXPU = false, bool FLOW = false>
 __global__ __launch_bounds__(256, LQCD_STAPLE_OCC) void gauge_force_kernel(GFArgs k) {
     const Geom& g = k.g;
     int chunk, p;
@@ -598,16 +620,16 @@ __global__ __launch_bounds__(256, LQCD_STAPLE_OCC) void gauge_force_kernel(GFArg
     }
     if (!valid) return;
     switch (mu) {
-    case 0: staple_links<MODE, 0, PART, R2, EXPU>(k, p, i, lane, own); break;
-    case 1: staple_links<MODE, 1, PART, R2, EXPU>(k, p, i, lane, own); break;
-    case 2: staple_links<MODE, 2, PART, R2, EXPU>(k, p, i, lane, own); break;
-    default: staple_links<MODE, 3, PART, R2, EXPU>(k, p, i, lane, own); break;
+    case 0: staple_links<MODE, 0, PART, R2, EXPU, false, FLOW>(k, p, i, lane, own); break;
+    case 1: staple_links<MODE, 1, PART, R2, EXPU, false, FLOW>(k, p, i, lane, own); break;
+    case 2: staple_links<MODE, 2, PART, R2, EXPU, false, FLOW>(k, p, i, lane, own); break;
+    default: staple_links<MODE, 3, PART, R2, EXPU, false, FLOW>(k, p, i, lane, own); break;
     }
 }
 
 // the TILE form (single GPU, links on the group, chunks of whole x-rows): MODE 0 / 1, optionally with the link update behind it.  LDS: the links of both parities of
 // the chunk, all three rows: 72 KiB per workgroup, two workgroups per CU.
-template <int MODE, bool EXPU>
+template <int MODE, bool EXPU, bool FLOW = false>
 __global__ __launch_bounds__(256, LQCD_STAPLE_TILE_OCC) void gauge_force_kernel_tile(GFArgs k) {
     const Geom& g = k.g;
     int chunk, p;
@@ -625,10 +647,10 @@ __global__ __launch_bounds__(256, LQCD_STAPLE_TILE_OCC) void gauge_force_kernel_
     }
     __syncthreads();
     switch (mu) {
-    case 0: staple_links<MODE, 0, false, true, EXPU, true>(k, p, i, lane, nullptr, own2); break;
-    case 1: staple_links<MODE, 1, false, true, EXPU, true>(k, p, i, lane, nullptr, own2); break;
-    case 2: staple_links<MODE, 2, false, true, EXPU, true>(k, p, i, lane, nullptr, own2); break;
-    default: staple_links<MODE, 3, false, true, EXPU, true>(k, p, i, lane, nullptr, own2); break;
+    case 0: staple_links<MODE, 0, false, true, EXPU, true, FLOW>(k, p, i, lane, nullptr, own2); break;
+    case 1: staple_links<MODE, 1, false, true, EXPU, true, FLOW>(k, p, i, lane, nullptr, own2); break;
+    case 2: staple_links<MODE, 2, false, true, EXPU, true, FLOW>(k, p, i, lane, nullptr, own2); break;
+    default: staple_links<MODE, 3, false, true, EXPU, true, FLOW>(k, p, i, lane, nullptr, own2); break;
     }
 }
 // the tile form applies: a chunk is 64 / XH whole x-rows of one (z, t) plane (XH a divisor of 64, the rows of a plane divide into chunks, every chunk full)
@@ -1002,6 +1024,7 @@ static GFArgs make_gfargs(lqcd_ctx_s* c, lqcd_gauge_s* U, lqcd_gauge_s* out, dou
     k.factor = factor;
     k.mu_only = -1; k.mu_out = 0;
     k.uout = nullptr; k.dt = 0.0; k.notproj = nullptr; k.reunit = 0;
+    k.xscale = 1.0; k.xread = 1;
     k.bm = make_block_map(c->geom, c->tun.md_remap ? c->tun.xcd_remap : 0, c->tun.xcd_nsub, c->tun.xcd_ysplit);
     for (int mu = 0; mu < 4; mu++) { k.ghost[mu] = c->gf_ghost[mu]; k.wrecv[mu] = c->gf_wrecv[mu]; k.wsend[mu] = c->gf_wsend[mu]; }
     return k;
@@ -1104,6 +1127,52 @@ static int staple_force_expu(lqcd_gauge_s* P, lqcd_gauge_s* U, double beta, doub
     if (k.reunit && !notproj) U->unitary_version = U->version;      // every link was projected: the field is on the group to rounding
     return LQCD_OK;
 }
+
+// One RK3 stage of the Wilson gradient flow (flow.hip): X <- xscale X + factor TA(G(U)) with G the staple force at beta = 6 (Z = TA(G), md.hip header), then
+// U <- exp(X) U.  Single GPU: ONE sweep, the staple_force_expu form with the accumulator scaled before the add (the new links go to the spare buffer and the
+// handles swap).  Partitioned: the ghost-link / staple-face exchange of staple_force, the sweep into X, then the exponential update as a second pass.  Nothing
+// is synchronised with the host: *notproj (device word, cleared by the caller) is set when some link was not projected back onto the group (md_reunitarize).
+namespace lqcd {
+int flow_stage(lqcd_gauge_s* U, double2* X, double xscale, double factor, bool xread, unsigned* notproj, bool two_rows) {
+    lqcd_ctx_s* c = U->ctx;
+    const int reunit = c->tun.md_reunitarize;
+    if (!any_partitioned(c)) {
+        if (!c->gauge_spare) {
+            HIPCHK(hipMalloc((void**)&c->gauge_spare, U->elems * sizeof(double2)));
+            HIPCHK(hipMemsetAsync(c->gauge_spare, 0, U->elems * sizeof(double2), c->stream));      // stride padding stays zero
+        }
+        GFArgs k = make_gfargs(c, U, U, 6.0, factor);
+        k.out = X;
+        k.uout = c->gauge_spare; k.dt = 1.0; k.notproj = notproj; k.reunit = reunit;
+        k.xscale = xscale; k.xread = xread ? 1 : 0;
+        const dim3 grid(2 * c->geom.nch);
+        if (two_rows && staple_tile_ok(c)) hipLaunchKernelGGL((gauge_force_kernel_tile<1, true, true>), grid, dim3(256), 0, c->stream, k);
+        else if (two_rows) hipLaunchKernelGGL((gauge_force_kernel<1, false, true, true, true>), grid, dim3(256), 0, c->stream, k);
+        else hipLaunchKernelGGL((gauge_force_kernel<1, false, false, true, true>), grid, dim3(256), 0, c->stream, k);
+        HIPCHK(hipGetLastError());
+        std::swap(U->data, c->gauge_spare);      // stream order: the next launch reads the new links
+        U->version++;
+        return LQCD_OK;
+    }
+    ARGCHK(c->local_peers.empty(), "gradient flow: this context belongs to an in-process PE grid");
+    LQCHK(gf_buffers(c));
+    for (int mu = 0; mu < 4; mu++)
+        if (c->geom.part[mu]) LQCHK(gauge_pack_face(U, mu, c->gf_gsend[mu]));
+    LQCHK(gf_exchange_rccl(c, c->gf_gsend, c->gf_ghost, true));
+    GFArgs k = make_gfargs(c, U, U, 6.0, factor);
+    k.out = X;
+    k.xscale = xscale; k.xread = xread ? 1 : 0;
+    LQCHK(launch_staple_faces(c, k));
+    LQCHK(gf_exchange_rccl(c, c->gf_wsend, c->gf_wrecv, false));
+    hipLaunchKernelGGL(gauge_force_kernel_part<4>, dim3(2 * c->geom.nch), dim3(256), 0, c->stream, k);
+    HIPCHK(hipGetLastError());
+    if (reunit) hipLaunchKernelGGL(link_exp_update_kernel<true>, dim3(link_grid(c->geom)), dim3(256), 0, c->stream, c->geom, U->data, 1.0, X, notproj);
+    else hipLaunchKernelGGL(link_exp_update_kernel<false>, dim3(link_grid(c->geom)), dim3(256), 0, c->stream, c->geom, U->data, 1.0, X, notproj);
+    HIPCHK(hipGetLastError());
+    U->version++;
+    return LQCD_OK;
+}
+}  // namespace lqcd
 
 // ---- single-direction entry points (the interface the reference's unchanged callers use, AbstractMD.jl:78-135)
 static int link_args(lqcd_gauge_t a, int ma, lqcd_gauge_t b, int mb, const char* who) {

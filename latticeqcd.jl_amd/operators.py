@@ -12,6 +12,7 @@ Reference call sites mirrored (paths relative to /root/reference):
   dot, clear_fermion!, add_fermion!, substitute_fermion!        src/updates/standardHMC.jl:54, src/md/standardMD.jl:50-51
   gauss_distribution_fermion!, Z4_distribution_fermi!           unusedfiles/measure_chiral_condensate.jl:180
   calculate_Plaquette                                           src/system/lqcd.jl:187-193
+  Gradientflow, flow!, Energy_density, Topological_charge       src/system/lqcd.jl:95-100,149-164
 
 Host arrays are numpy complex128, C order, with the memory image of the Julia arrays:
   gauge U[mu,t,z,y,x,b,a], Wilson psi[s,t,z,y,x,c], staggered psi[t,z,y,x,c]   (local sub-lattice of this rank).
@@ -266,6 +267,81 @@ def calculate_Polyakov_loop(U, temp1=None, temp2=None):
     re, im = C.c_double(0), C.c_double(0)
     check(_l.lib().lqcd_gauge_polyakov(U._h, C.byref(re), C.byref(im)))
     return complex(re.value, im.value)
+
+
+# ---- gradient flow and the observables along it (src/system/lqcd.jl:95-100,149-164; include/lqcd_hip.h "gradient flow")
+FLOW_OBSERVABLES = ("p", "E_plaq", "E_clov", "Q_plaq", "Q_clov", "Q_impr")
+FLOW_TABLE_COLUMNS = ("t",) + FLOW_OBSERVABLES
+
+
+class Gradientflow:
+    """Gradientflow(U; Nflow, eps) (lqcd.jl:99): Nflow RK3 steps of size eps per flow_ call."""
+
+    def __init__(self, U=None, Nflow=1, eps=0.01):
+        self.Nflow = int(Nflow)
+        self.eps = float(eps)
+
+
+def flow_(U, gf):
+    """flow!(Usmr, gradientflow) (lqcd.jl:153): gf.Nflow RK3 steps of the Wilson flow, in place on the device."""
+    check(_l.lib().lqcd_gradient_flow(U._h, C.c_double(gf.eps), int(gf.Nflow)))
+    return U
+
+
+def gauge_flow_observables(U):
+    """(p, E_plaq, E_clov, Q_plaq, Q_clov, Q_impr) of the links as they are (lqcd_gauge_flow_observables); Q_impr is NaN on a partitioned lattice."""
+    obs = (C.c_double * 6)()
+    check(_l.lib().lqcd_gauge_flow_observables(U._h, obs))
+    return dict(zip(FLOW_OBSERVABLES, list(obs)))
+
+
+def calculate_energy_density(U, kind="clover"):
+    """Energy_density (lqcd.jl:155-162): E per site in lattice units from the plaquette ("plaquette") or the clover field strength ("clover")."""
+    key = {"plaquette": "E_plaq", "clover": "E_clov"}.get(kind)
+    if key is None:
+        raise ValueError(f"calculate_energy_density: kind {kind!r} (plaquette | clover)")
+    return gauge_flow_observables(U)[key]
+
+
+def calculate_topological_charge(U, kind="clover"):
+    """Topological_charge (lqcd.jl:155-162) with kind plaquette | clover | improved."""
+    key = {"plaquette": "Q_plaq", "clover": "Q_clov", "improved": "Q_impr"}.get(kind)
+    if key is None:
+        raise ValueError(f"calculate_topological_charge: kind {kind!r} (plaquette | clover | improved)")
+    return gauge_flow_observables(U)[key]
+
+
+def gradient_flow_measure(U, eps=0.01, numflow=100, every=1):
+    """The driver's flow schedule resident on the device: numflow steps, the observables after every `every`-th step.  Returns an array of
+    numflow // every rows, columns FLOW_TABLE_COLUMNS = (t, p, E_plaq, E_clov, Q_plaq, Q_clov, Q_impr)."""
+    nrows = int(numflow) // int(every)
+    tab = np.zeros((nrows, len(FLOW_TABLE_COLUMNS)), dtype=np.float64)
+    check(_l.lib().lqcd_gradient_flow_measure(U._h, C.c_double(eps), int(numflow), int(every),
+                                              tab.ctypes.data_as(C.POINTER(C.c_double))))
+    return tab
+
+
+def _crossing(t, y, target):
+    """First t where y passes `target` from below, linear interpolation; NaN when it does not."""
+    for i in range(len(t) - 1):
+        if y[i] < target <= y[i + 1]:
+            return float(t[i] + (target - y[i]) * (t[i + 1] - t[i]) / (y[i + 1] - y[i]))
+    return float("nan")
+
+
+def flow_scales(table, energy="E_clov", target=0.3):
+    """(t0, w0) from a gradient_flow_measure table: t0 where t^2 E = target, w0 = sqrt of the t where t d(t^2 E)/dt = target (the derivative by
+    differences of neighbouring rows, at their midpoints).  NaN for a scale whose target the table does not reach."""
+    tab = np.asarray(table, dtype=np.float64)
+    t = tab[:, 0]
+    F = t * t * tab[:, FLOW_TABLE_COLUMNS.index(energy)]
+    t0 = _crossing(t, F, target)
+    if len(t) < 2:
+        return t0, float("nan")
+    tm = 0.5 * (t[1:] + t[:-1])
+    W = tm * np.diff(F) / np.diff(t)
+    w2 = _crossing(tm, W, target)
+    return t0, float(np.sqrt(w2)) if w2 == w2 else float("nan")
 
 
 def reunitarize_(U):
