@@ -412,6 +412,21 @@ int lqcd_gauge_flow_observables(lqcd_gauge_t V, double obs[LQCD_FLOW_NOBS]);    
  * table receives nsteps/every rows [t, p, E_plaq, E_clov, Q_plaq, Q_clov, Q_impr] (row-major).  One device-to-host copy, at the end */
 int lqcd_gradient_flow_measure(lqcd_gauge_t V, double eps, int nsteps, int every, double* table);
 
+/* ---------------------------------------------------------------- quenched heatbath and overrelaxation (src/updates/heatbath.jl:1-44)
+ * Plaquette action S_g = -(beta/3) sum_plaq Re tr U_p.  One heatbath sweep: mu = 0..3, even then odd sites, every link of that parity in place by
+ * Cabibbo-Marinari over the SU(2) subgroups (1,2), (1,3), (2,3) (Kennedy-Pendleton / Creutz sampling); one overrelaxation (OR) sweep: the same order with
+ * the microcanonical reflection (no random numbers, independent of beta).  Every updated link is projected back onto SU(3) as lqcd_gauge_reunitarize does.
+ * Random numbers are keyed by (seed, absolute sweep number first_sweep + i, mu, global site, subgroup): a run split into calls gives the same bits, on
+ * every partitioning.  A draw that takes more than itmax trials (ITERATION_MAX) leaves its subgroup unchanged and the call returns
+ * LQCD_ERR_NOT_CONVERGED (lqcd_last_error gives the count).  beta < 0, nsweeps < 0, nor < 0, itmax < 1 or a null plaq: LQCD_ERR_ARG, U untouched.
+ * Collective on a partitioned lattice (RCCL or the peer backend); an in-process PE grid answers LQCD_ERR_UNSUPPORTED.  Draw order: csrc/heatbath.hip. */
+/* nsweeps x (one heatbath sweep + nor OR sweeps); update!(::Heatbathupdate, U) (heatbath.jl:35-43) is nsweeps = 1, nor = useOR ? numOR : 0 */
+int lqcd_gauge_heatbath(lqcd_gauge_t U, double beta, int nsweeps, int nor, int itmax, uint64_t seed, uint64_t first_sweep);
+int lqcd_gauge_overrelax(lqcd_gauge_t U, int nsweeps);                     /* overrelaxation!(U, hb) */
+/* lqcd_gauge_heatbath with plaq[i] = the plaquette (as lqcd_gauge_plaquette, bit for bit on a single domain) after heatbath + OR block i; every rank gets
+ * the same values.  One device-to-host copy, at the end */
+int lqcd_gauge_heatbath_measure(lqcd_gauge_t U, double beta, int nsweeps, int nor, int itmax, uint64_t seed, uint64_t first_sweep, double* plaq);
+
 /* the SURVEY.md 8(d) protocol: every application between its own HIP events, median and mean over reps */
 int lqcd_bench_dslash_median(lqcd_op_t op, lqcd_spinor_t out, lqcd_spinor_t in, int dagger, int warm, int reps, double* median_ms,
                              double* mean_ms);

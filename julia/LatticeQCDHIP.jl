@@ -32,14 +32,14 @@ import Base: similar, adjoint
 import Gaugefields: AbstractGaugefields, GaugeAction, Initialize_Gaugefields, substitute_U!, exptU!, Traceless_antihermitian_add!, calc_dSdUμ!,
     evaluate_GaugeAction, initialize_TA_Gaugefields, gauss_distribution!, calc_smearedU, println_verbose_level1,
     println_verbose_level2, println_verbose_level3, get_myrank, calculate_Plaquette, calculate_Polyakov_loop, load_BridgeText!, load_gaugefield!,
-    CovNeuralnet, CovLayer, STOUT_Layer, back_prop, Gradientflow, flow!
+    CovNeuralnet, CovLayer, STOUT_Layer, back_prop, Gradientflow, flow!, Heatbath, heatbath!, overrelaxation!
 import LatticeDiracOperators: Dirac_operator, DdagD_operator, FermiAction, Initialize_pseudofermion_fields,
     gauss_sampling_in_action!, sample_pseudofermions!, evaluate_FermiAction, calc_UdSfdU!, solve_DinvX!, shiftedcg,
     clear_fermion!, substitute_fermion!, add_fermion!, gauss_distribution_fermion!, Z4_distribution_fermi!,
     AbstractFermionfields_4D
 
 export Initialize_HIPGaugefields, HIPLattice, HIPLink, HIPTALink, HIPFermion, HIPDirac, HIPFermiAction, reunitarize!, activate!, deactivate!,
-    HIPGradientflow, flow_observables, energy_density, topological_charge, gradient_flow_measure
+    HIPGradientflow, flow_observables, energy_density, topological_charge, gradient_flow_measure, HIPHeatbath, heatbath_measure
 
 const LIB = get(ENV, "LQCD_HIP_LIB", joinpath(@__DIR__, "..", "latticeqcd.jl_amd", "csrc", "liblqcd_hip.so"))
 
@@ -352,6 +352,36 @@ function gradient_flow_measure(U::Vector{HIPLink}, eps::Real, numflow::Integer, 
     tab = zeros(Float64, 7, nrows)       # column-major 7 x nrows = the C side's row-major nrows x 7
     check(ccall((:lqcd_gradient_flow_measure, LIB), Cint, (Ptr{Cvoid}, Float64, Cint, Cint, Ptr{Float64}), whole(U).h, Float64(eps), numflow, every, tab))
     return [tab[j, i] for i = 1:nrows, j = 1:7]
+end
+
+# the quenched heatbath (src/updates/heatbath.jl): Heatbathupdate builds `Heatbath(U, β, ITERATION_MAX = ITERATION_MAX)` (heatbath.jl:27) and update!
+# (:35-43) calls `heatbath!(U, hb)` and `overrelaxation!(U, hb)` -- Gaugefields generics, imported above and extended here for the binding's links.
+# The struct's field is typed Union{Heatbath_update{Dim,T},Heatbath{T}} (heatbath.jl:2), so a HIPHeatbath is refused when the struct is built: the
+# driver needs the one edit of INTEGRATION.md (that field untyped).  The seed and the sweep counter key the device's random numbers (include/lqcd_hip.h).
+mutable struct HIPHeatbath
+    β::Float64
+    ITERATION_MAX::Int
+    seed::UInt64
+    sweep::UInt64
+end
+Heatbath(U::Vector{HIPLink}, β; ITERATION_MAX = 10^5, seed = rand(UInt64)) = HIPHeatbath(Float64(β), ITERATION_MAX, UInt64(seed), UInt64(0))
+function heatbath!(U::Vector{HIPLink}, hb::HIPHeatbath)
+    check(ccall((:lqcd_gauge_heatbath, LIB), Cint, (Ptr{Cvoid}, Float64, Cint, Cint, Cint, UInt64, UInt64), whole(U).h, hb.β, 1, 0,
+                hb.ITERATION_MAX, hb.seed, hb.sweep))
+    hb.sweep += 1
+    return U
+end
+function overrelaxation!(U::Vector{HIPLink}, hb::HIPHeatbath)       # no random numbers: the sweep counter stays
+    check(ccall((:lqcd_gauge_overrelax, LIB), Cint, (Ptr{Cvoid}, Cint), whole(U).h, 1))
+    return U
+end
+# nsweeps x (heatbath! + numOR x overrelaxation!) resident on the device; the plaquette after every block, one copy to the host at the end
+function heatbath_measure(U::Vector{HIPLink}, hb::HIPHeatbath, nsweeps::Integer; numOR::Integer = 0)
+    plaq = zeros(Float64, nsweeps)
+    check(ccall((:lqcd_gauge_heatbath_measure, LIB), Cint, (Ptr{Cvoid}, Float64, Cint, Cint, Cint, UInt64, UInt64, Ptr{Float64}), whole(U).h, hb.β,
+                nsweeps, numOR, hb.ITERATION_MAX, hb.seed, hb.sweep, plaq))
+    hb.sweep += nsweeps
+    return plaq
 end
 
 # substitute_U!(Uold, U) / substitute_U!(U, Uold) (standardHMC.jl:45,84) and substitute_U!(U[mu], W) (AbstractMD.jl:93)

@@ -282,6 +282,7 @@ extern "C" int lqcd_ctx_destroy(lqcd_ctx_t c) {
     for (lqcd_gauge_s*& t : c->stout_tmp) if (t) { (void)hipFree(t->data); (void)hipFree(t->data12); (void)hipFree(t->data12d); delete t; t = nullptr; }
     (void)hipFree(c->gauge_spare);
     (void)hipFree(c->flow_x); (void)hipFree(c->flow_partial); (void)hipFree(c->flow_tab);
+    (void)hipFree(c->hb_tab);
     (void)hipFree(c->clover_ext); (void)hipFree(c->clover_ext_buf[0]); (void)hipFree(c->clover_ext_buf[1]);
     if (c->has_comm && !c->peer.on) { ncclCommDestroy(c->comm); ncclCommDestroy(c->comm_red); }
     comm_teardown(c);      // the peer-mapped backend's windows (comm.hip)

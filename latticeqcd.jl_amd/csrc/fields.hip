@@ -384,6 +384,37 @@ int plaquette_local_sum(lqcd_gauge_s* g, const double2* const ghost[4], double* 
     return LQCD_OK;
 }
 
+// one workgroup: *out = the partials added in index order from 0.0, plain adds -- the order and the arithmetic of plaquette_local_sum's host loop
+__global__ __launch_bounds__(256) void plaquette_final_kernel(const double* __restrict__ partial, int nb, double* __restrict__ out) {
+    __shared__ double buf[2048];
+    double s = 0.0;
+    for (int b0 = 0; b0 < nb; b0 += 2048) {
+        const int n = nb - b0 < 2048 ? nb - b0 : 2048;
+        for (int j = threadIdx.x; j < n; j += 256) buf[j] = partial[b0 + j];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int j = 0; j < n; j++) s += buf[j];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = s;
+}
+
+// plaquette_local_sum without the host: the sum stays on the device in *d_sum, bit for bit the host's (heatbath.hip: a plaquette per sweep, one copy at the end)
+int plaquette_local_sum_device(lqcd_gauge_s* g, const double2* const ghost[4], double* d_sum) {
+    lqcd_ctx_s* c = g->ctx;
+    PlaqArgs k;
+    k.g = c->geom;
+    k.gauge = g->data;
+    for (int mu = 0; mu < 4; mu++) k.ghost[mu] = ghost ? ghost[mu] : nullptr;
+    k.partial = c->d_partial;
+    const int nt = 2 * c->geom.Vh, nb = (nt + 127) / 128;
+    hipLaunchKernelGGL(plaquette_kernel, dim3(nb), dim3(128), 0, c->stream, k);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(plaquette_final_kernel, dim3(1), dim3(256), 0, c->stream, c->d_partial, nb, d_sum);
+    HIPCHK(hipGetLastError());
+    return LQCD_OK;
+}
+
 int gauge_pack_face(lqcd_gauge_s* g, int mu, double2* dst) {
     lqcd_ctx_s* c = g->ctx;
     const int nt = 2 * face_half_sites(c->geom, mu);

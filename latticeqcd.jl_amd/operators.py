@@ -13,6 +13,7 @@ Reference call sites mirrored (paths relative to /root/reference):
   gauss_distribution_fermion!, Z4_distribution_fermi!           unusedfiles/measure_chiral_condensate.jl:180
   calculate_Plaquette                                           src/system/lqcd.jl:187-193
   Gradientflow, flow!, Energy_density, Topological_charge       src/system/lqcd.jl:95-100,149-164
+  Heatbath, heatbath!, overrelaxation!, Heatbathupdate, update!  src/updates/heatbath.jl:1-44, src/updates/AbstractUpdate.jl:59-108
 
 Host arrays are numpy complex128, C order, with the memory image of the Julia arrays:
   gauge U[mu,t,z,y,x,b,a], Wilson psi[s,t,z,y,x,c], staggered psi[t,z,y,x,c]   (local sub-lattice of this rank).
@@ -342,6 +343,68 @@ def flow_scales(table, energy="E_clov", target=0.3):
     W = tm * np.diff(F) / np.diff(t)
     w2 = _crossing(tm, W, target)
     return t0, float(np.sqrt(w2)) if w2 == w2 else float("nan")
+
+
+# ---- quenched heatbath and overrelaxation (src/updates/heatbath.jl; include/lqcd_hip.h "quenched heatbath", csrc/heatbath.hip)
+class Heatbath:
+    """Heatbath(U, beta; ITERATION_MAX) of the checkerboard heatbath: beta, the trial cap, the seed and the absolute number of the next heatbath sweep
+    (the random numbers are keyed by it, so a run split into calls gives the bits of one call).  Only heatbath sweeps advance the counter:
+    overrelaxation draws no random numbers."""
+
+    def __init__(self, U=None, beta=5.7, ITERATION_MAX=10**5, seed=111):
+        self.beta = float(beta)
+        self.ITERATION_MAX = int(ITERATION_MAX)
+        self.seed = int(seed)
+        self.sweep = 0
+
+
+def heatbath_(U, hb):
+    """heatbath!(U, hb): one heatbath sweep (Cabibbo-Marinari over the three SU(2) subgroups, every link once), in place on the device."""
+    check(_l.lib().lqcd_gauge_heatbath(U._h, C.c_double(hb.beta), 1, 0, hb.ITERATION_MAX, C.c_uint64(hb.seed), C.c_uint64(hb.sweep)))
+    hb.sweep += 1
+    return U
+
+
+def overrelaxation_(U, hb=None):
+    """overrelaxation!(U, hb): one microcanonical sweep (independent of beta, no random numbers)."""
+    check(_l.lib().lqcd_gauge_overrelax(U._h, 1))
+    return U
+
+
+def heatbath_measure(U, hb, nsweeps, numOR=0):
+    """nsweeps x (heatbath_ + numOR x overrelaxation_) resident on the device; returns the plaquette after every block (numpy array, one copy at the end)."""
+    plaq = np.zeros(int(nsweeps), dtype=np.float64)
+    check(_l.lib().lqcd_gauge_heatbath_measure(U._h, C.c_double(hb.beta), int(nsweeps), int(numOR), hb.ITERATION_MAX, C.c_uint64(hb.seed),
+                                               C.c_uint64(hb.sweep), plaq.ctypes.data_as(C.POINTER(C.c_double))))
+    hb.sweep += int(nsweeps)
+    return plaq
+
+
+class Heatbathupdate:
+    """Heatbathupdate(U, gauge_action, quench; useOR, numOR, isevenodd, beta, ITERATION_MAX) (heatbath.jl:8-33); update_(method, U) is
+    update!(method, U) (heatbath.jl:35-43): one heatbath sweep, then numOR overrelaxation sweeps when useOR.  Quenched only, as in the reference.
+    isevenodd = False (the reference's Heatbath_update for general actions) runs the same checkerboard sweep: for the plaquette action, the only
+    action on this path, it samples the same distribution."""
+
+    def __init__(self, U, gauge_action=None, quench=True, useOR=False, numOR=0, isevenodd=True, beta=2.3, ITERATION_MAX=10**5, seed=111, **kw):
+        assert quench, "Heatbath update is only for quench case!"
+        self.heatbath = Heatbath(U, kw.pop("β", beta), ITERATION_MAX=ITERATION_MAX, seed=seed)
+        if kw:
+            raise TypeError(f"Heatbathupdate: unexpected arguments {sorted(kw)}")
+        self.isevenodd = bool(isevenodd)
+        self.numOR = int(numOR)
+        self.useOR = bool(useOR)
+
+
+def update_(method, U):
+    """update!(updatemethod::Heatbathupdate, U) (heatbath.jl:35-43) as ONE library call: heatbath sweep + numOR OR sweeps when useOR."""
+    if not isinstance(method, Heatbathupdate):
+        raise LQCDError(_l.ERR_UNSUPPORTED, "update_: only Heatbathupdate runs through this entry point")
+    hb = method.heatbath
+    nor = method.numOR if method.useOR else 0
+    check(_l.lib().lqcd_gauge_heatbath(U._h, C.c_double(hb.beta), 1, int(nor), hb.ITERATION_MAX, C.c_uint64(hb.seed), C.c_uint64(hb.sweep)))
+    hb.sweep += 1
+    return True
 
 
 def reunitarize_(U):
