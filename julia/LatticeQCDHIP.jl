@@ -5,7 +5,7 @@
 # tests/golden/ref_caller_inventory.json and checked against this file by tests/test_julia_binding_static.py) but NEVER EXECUTED: there is no Julia
 # in the build image (SURVEY.md section 0.3).  Everything below the `ccall`s is exercised through the same C ABI by tests/ (Python ctypes).
 # The file is deliberately thin: every method is one ccall plus error translation; there is NO module-level mutable state (the lazy fusion of the
-# callers' per-direction link-call triples lives below the C ABI, csrc/md.hip).
+# callers' per-direction link-call triples lives below the C ABI, csrc/links.hip).
 #
 # How it plugs in.  The reference has no FFI; its seam is multiple dispatch on types of Gaugefields.jl / LatticeDiracOperators.jl.  This
 # module therefore EXTENDS the packages' own generic functions (`import Gaugefields: substitute_U!, ...`) with methods on device-backed
@@ -156,7 +156,7 @@ views(::Type{T}, g::HIPGaugeStorage) where {T<:AnyLink} = T[T(g, Cint(μ - 1)) f
 # exptU!(expU, t, p[μ]) -> mul!(W, expU, U[μ]) -> substitute_U!(U[μ], W) and calc_dSdUμ!(dSdUμ, ..) -> mul!(temp1, U[μ], dSdUμ) ->
 # Traceless_antihermitian_add!(p[μ], factor, temp1).  Each generic below is ONE stateless ccall (lqcd_link_exp, lqcd_link_mul, lqcd_link_copy,
 # lqcd_link_staple, lqcd_link_add_ta); the LIBRARY records the first two calls of a triple per context, launches one fused kernel at the third and
-# turns four completed triples of one update into one four-direction launch (csrc/md.hip "lazy link triples", tunable lazy_links) -- every other
+# turns four completed triples of one update into one four-direction launch (csrc/links.hip "lazy link triples", tunable lazy_links) -- every other
 # entry point that touches a gauge-shaped field runs what is recorded first.  The temporaries of a completed triple (expU, W, dSdUμ, temp1) are not
 # written; the callers return them to their pool unread.  set_param!(lattice, "lazy_links", 0) makes every call launch its own kernel.
 slotof(l::AnyLink) = getfield(l, :slot)

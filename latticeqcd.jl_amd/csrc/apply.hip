@@ -416,7 +416,7 @@ int check_full(lqcd_op_s* op, lqcd_spinor_s* a, lqcd_spinor_s* b, const char* wh
         set_error(std::string(who) + ": not available for the Domainwall operator (mul!, DdagD, the CG and the action entry points are)");
         return LQCD_ERR_UNSUPPORTED;
     }
-    return links_flush_of(op);      // the operator reads its links: recorded single-direction link operations run first (md.hip)
+    return links_flush_of(op);      // the operator reads its links: recorded single-direction link operations run first (links.hip)
 }
 
 int op_apply_async(lqcd_op_s* op, lqcd_spinor_s* out, lqcd_spinor_s* in, int dagger, double* norm_partial, const double* skip_flag) {
@@ -435,7 +435,7 @@ using namespace lqcd;
 // ---------------------------------------------------------------------------------- C API: operator
 extern "C" int lqcd_op_create(lqcd_ctx_t ctx, lqcd_op_t* op, int kind, lqcd_gauge_t g, double km, double r, const int bc[4]) {
     ARGCHK(kind != LQCD_DOMAINWALL, "lqcd_op_create: the Domainwall operator is made by lqcd_op_create_domainwall (it needs M and L5)");
-    LQCHK(lqcd::links_flush_of(g));      // recorded single-direction link operations run first (md.hip)
+    LQCHK(lqcd::links_flush_of(g));      // recorded single-direction link operations run first (links.hip)
     ARGCHK(ctx && op && g && bc, "lqcd_op_create: null argument");
     ARGCHK(kind == LQCD_WILSON || kind == LQCD_STAGGERED, "lqcd_op_create: Dirac_operator not supported");
     ARGCHK(g->ctx == ctx, "lqcd_op_create: gauge field belongs to another context");
@@ -462,7 +462,7 @@ extern "C" int lqcd_op_destroy(lqcd_op_t op) {
 // Dirac_operator = "WilsonClover", Clover_coefficient (parameter_structs.jl:125; test/test_wilsonclover.toml:9): D_sw = D + (A - 1),
 // A = 1 + i kappa c_sw sum_{mu<nu} sigma_{mu nu} F_{mu nu} (clover.hip).  csw = 0 switches the term off again.
 extern "C" int lqcd_op_set_clover(lqcd_op_t op, double csw) {
-    LQCHK(lqcd::links_flush_of(op));      // recorded single-direction link operations run first (md.hip)
+    LQCHK(lqcd::links_flush_of(op));      // recorded single-direction link operations run first (links.hip)
     ARGCHK(op, "lqcd_op_set_clover: null argument");
     ARGCHK(op->kind == LQCD_WILSON, "lqcd_op_set_clover: the clover term belongs to the Wilson operator");
     lqcd_ctx_s* c = op->ctx;
@@ -514,7 +514,7 @@ extern "C" int lqcd_op_apply_DdagD(lqcd_op_t op, lqcd_spinor_t out, lqcd_spinor_
 }
 
 extern "C" int lqcd_op_hop(lqcd_op_t op, lqcd_spinor_t out, lqcd_spinor_t in, int dagger) {
-    LQCHK(lqcd::links_flush_of(op));      // recorded single-direction link operations run first (md.hip)
+    LQCHK(lqcd::links_flush_of(op));      // recorded single-direction link operations run first (links.hip)
     ARGCHK(op && out && in && out->ctx == op->ctx && in->ctx == op->ctx && out->kind == op->kind && in->kind == op->kind,
            "lqcd_op_hop: bad arguments");
     ARGCHK((out->subset == LQCD_EVEN && in->subset == LQCD_ODD) || (out->subset == LQCD_ODD && in->subset == LQCD_EVEN),

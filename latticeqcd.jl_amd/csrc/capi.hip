@@ -398,7 +398,7 @@ extern "C" int lqcd_ctx_set_param(lqcd_ctx_t c, const char* key, int value) {
 }
 extern "C" int lqcd_ctx_get_param(lqcd_ctx_t c, const char* key, int* value) {
     ARGCHK(c && key && value, "lqcd_ctx_get_param: null");
-    // read-only views of the recorded link operations (md.hip): the open triple (0 none, 1 exp, 2 exp + mul, 3 staple, 4 staple + mul), deferred triples
+    // read-only views of the recorded link operations (links.hip): the open triple (0 none, 1 exp, 2 exp + mul, 3 staple, 4 staple + mul), deferred triples
     if (!strcmp(key, "dw_active")) { *value = c->tun.dw_active; return LQCD_OK; }
     if (!strcmp(key, "adopt_thread")) {      // 1: the calling thread is the context's own (the creating one, or the last to set adopt_thread)
         std::lock_guard<std::mutex> lk(g_live_mu);
@@ -478,7 +478,7 @@ extern "C" int lqcd_ctx_link_local(lqcd_ctx_t* ctxs, int n) {
 
 // ---------------------------------------------------------------------------------- plaquette (single rank or RCCL ranks)
 extern "C" int lqcd_gauge_plaquette(lqcd_gauge_t g, double* plaq) {
-    LQCHK(lqcd::links_flush_of(g));      // recorded single-direction link operations run first (md.hip)
+    LQCHK(lqcd::links_flush_of(g));      // recorded single-direction link operations run first (links.hip)
     ARGCHK(g && plaq, "lqcd_gauge_plaquette: null");
     lqcd_ctx_s* c = g->ctx;
     HIPCHK(hipSetDevice(c->device));

@@ -11,12 +11,9 @@
 // input (out = tmp - kappa H x): 960 B/site on top of the Dslash's 960; folding it into the stencil epilogue (compulsory
 // 1536 B/site in total) is the obvious next step.
 #include "lqcd_internal.h"
+#include "gauge_staple.h"      // the exchange hooks of the staple force (staple.hip): forward ghost links, grouped send / recv of buffers of 4 matrices per face site
 
 #include <complex>
-
-// exchange hooks of the staple force (md.hip): buffers of 4 matrices per face site and grouped send / recv
-int gf_buffers(lqcd_ctx_s* c);
-int gf_exchange_rccl(lqcd_ctx_s* c, double2* const sendb[4], double2* const recvb[4], bool to_backward);
 
 namespace lqcd {
 
@@ -410,10 +407,7 @@ static int clover_q_transport(lqcd_ctx_s* c, const lqcd_gauge_s* U, double2* q0,
     const bool part = any_partitioned(c);
     if (part) {
         ARGCHK(c->local_peers.empty(), "clover term: not available on an in-process PE grid");
-        LQCHK(gf_buffers(c));
-        for (int mu = 0; mu < 4; mu++)
-            if (c->geom.part[mu]) LQCHK(gauge_pack_face(const_cast<lqcd_gauge_s*>(U), mu, c->gf_gsend[mu]));
-        LQCHK(gf_exchange_rccl(c, c->gf_gsend, c->gf_ghost, true));
+        LQCHK(gauge_halo_links(const_cast<lqcd_gauge_s*>(U)));
     }
     CloverQArgs k;
     k.g = c->geom;
@@ -794,7 +788,7 @@ static int clover_ext_build(lqcd_ctx_s* c, const lqcd_gauge_s* U, const double2*
     return LQCD_OK;
 }
 
-// ---- stout back-propagation on a partitioned lattice (md.hip, "stout smearing"): the same 24-loop gather as stout_gather_kernel, reading the links and the N matrices
+// ---- stout back-propagation on a partitioned lattice (stout.hip): the same 24-loop gather as stout_gather_kernel, reading the links and the N matrices
 // (four per site, carried in planes 0..3 of a Lambda-shaped buffer) from the halo-extended block -- it reaches n + mu - nu, a corner of the neighbouring ranks.
 __global__ __launch_bounds__(256) void stout_gather_ext_kernel(Geom g, ForceSrc src, double2* __restrict__ G, double rho) {
     const int p = blockIdx.x & 1, i = (blockIdx.x >> 1) * 64 + (threadIdx.x & 63), mu = threadIdx.x >> 6;

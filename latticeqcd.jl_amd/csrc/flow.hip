@@ -3,10 +3,10 @@
 // Topological_charge with kinds plaquette / clover / improved; defaults src/system/parameter_structs.jl:161-164).
 //
 // Conventions (directions 0..3 = x, y, z, t; TA(M) = (M - M^+)/2 - tr(M - M^+)/6):
-//   flow      dV/dt = Z(V) V with Z = TA(G), G the staple force of lqcd_gauge_force at beta = 6 (md.hip); one Euler step is a stout step with rho = eps.
+//   flow      dV/dt = Z(V) V with Z = TA(G), G the staple force of lqcd_gauge_force at beta = 6 (staple.hip); one Euler step is a stout step with rho = eps.
 //             Luscher's RK3 (JHEP 08 (2010) 071) with one gauge-shaped accumulator X, every stage  X <- a X + f TA(G(W)),  W <- exp(X) W:
 //               (a, f) = (0, eps/4), (-17/9, 8 eps/9), (-1, 3 eps/4).
-//             Single GPU: one staple sweep per stage (md.hip flow_stage: the fused momentum + link sweep with the accumulator scaled before the add);
+//             Single GPU: one staple sweep per stage (staple.hip flow_stage: the fused momentum + link sweep with the accumulator scaled before the add);
 //             partitioned: the staple force's ghost-link / staple-face exchange, the sweep into X, then the exponential update as a second pass.
 //   fields    for n closed loops through x in the (mu, nu) plane, all run the way of the plaquette +mu +nu -mu -nu:  G_mu nu(x) = TA(sum of loops) / n;
 //             loop sets "plaquette" (n = 1), "clover" (the four leaves, n = 4), "rect" (the eight 1x2 and 2x1 rectangles with a corner at x, n = 8).
@@ -20,6 +20,7 @@
 //   order: the results are bitwise reproducible run to run.  Partitioned lattices read the links through clover.hip's depth-1 halo-extended block
 //   (corners included): the rectangles need depth 2, so Q_impr is NaN there.
 #include "lqcd_internal.h"
+#include "gauge_staple.h"
 
 #include <cmath>
 #include <cstring>
@@ -27,9 +28,6 @@
 #include <vector>
 
 namespace lqcd {
-
-int flow_stage(lqcd_gauge_s* U, double2* X, double xscale, double factor, bool xread, unsigned* notproj, bool two_rows);      // md.hip
-int gauge_ext_links(lqcd_ctx_s* c, const lqcd_gauge_s* U, const double2** ext, int E[4], size_t* n);                      // clover.hip
 
 constexpr int FLOW_RAW = 5;                 // raw sums per measurement: sum (3 - Re tr P), -sum tr G^2 (clover), the eps contraction of each loop set
 constexpr int FLOW_OBS_THREADS = 128;
@@ -142,13 +140,7 @@ __device__ __forceinline__ void obs_field(cd (&G)[9], double& retr, const ObsArg
         for (int e = 0; e < 9; e++) S[e] = S[e] + P[e];
     }
     retr = S[0].re + S[4].re + S[8].re;
-    const double f = 0.5 / (double)nl;
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int q = 0; q < 3; q++) G[r * 3 + q] = mk(f * (S[r * 3 + q].re - S[q * 3 + r].re), f * (S[r * 3 + q].im + S[q * 3 + r].im));
-    const double tr = (G[0].im + G[4].im + G[8].im) / 3.0;
-    G[0].im -= tr; G[4].im -= tr; G[8].im -= tr;
+    ta3(G, S, 0.5 / (double)nl);
 }
 __device__ __forceinline__ double tr_re(const cd (&A)[9], const cd (&B)[9]) {      // Re tr A B
     double s = 0.0;

@@ -27,7 +27,7 @@
 //   cap         itmax trials per draw (the reference's ITERATION_MAX).  A draw that runs out leaves its subgroup alone and adds to a device counter; the call
 //               then returns LQCD_ERR_NOT_CONVERGED with the count in lqcd_last_error().  The links stay on the group.
 // Partitioned lattices (RCCL or the peer backend): before every (mu, parity) launch the forward ghost links and the received lower staples are refreshed
-// by the staple force's exchange (md.hip staple_halo_args), 8 refreshes per sweep.  An in-process PE grid answers LQCD_ERR_UNSUPPORTED.
+// by the staple force's exchange (staple.hip staple_halo_args), 8 refreshes per sweep.  An in-process PE grid answers LQCD_ERR_UNSUPPORTED.
 #include "lqcd_internal.h"
 #include "gauge_staple.h"
 
@@ -36,13 +36,7 @@
 #include <string>
 #include <vector>
 
-int gf_buffers(lqcd_ctx_s* c);                                                                           // md.hip
-int gf_exchange_rccl(lqcd_ctx_s* c, double2* const sendb[4], double2* const recvb[4], bool to_backward);      // md.hip
-
 namespace lqcd {
-
-int staple_halo_args(lqcd_gauge_s* U, GFArgs& k);                                        // md.hip
-int plaquette_local_sum_device(lqcd_gauge_s* g, const double2* const ghost[4], double* d_sum);      // fields.hip
 
 constexpr uint64_t HB_SALT = 0x6865617462617468ull;     // "heatbath"
 constexpr uint64_t HB_DIR_J = 1ull << 40;               // first draw of the direction, past every trial block
@@ -127,7 +121,7 @@ __device__ __forceinline__ void su2_update(cd (&U)[9], cd (&W)[9], const HBArgs&
     if constexpr (SG < 2) su2_rows<I, J>(W, r0, r1, r2, r3);
 }
 
-// one (mu, parity) launch: lane = site of parity p; run-time direction (the partitioned form of md.hip gauge_force_kernel_part)
+// one (mu, parity) launch: lane = site of parity p; run-time direction (the partitioned form of staple.hip gauge_force_kernel_part)
 template <bool OR, bool PART>
 __global__ __launch_bounds__(HB_THREADS) void heatbath_kernel(HBArgs h) {
     const GFArgs& k = h.s;
@@ -218,10 +212,7 @@ static int hb_sweep(lqcd_gauge_s* U, bool over, double beta, int itmax, uint64_t
 static int hb_plaquette(lqcd_gauge_s* U, double* d_sum) {
     lqcd_ctx_s* c = U->ctx;
     if (!any_partitioned(c)) return plaquette_local_sum_device(U, nullptr, d_sum);
-    LQCHK(gf_buffers(c));
-    for (int mu = 0; mu < 4; mu++)
-        if (c->geom.part[mu]) LQCHK(gauge_pack_face(U, mu, c->gf_gsend[mu]));
-    LQCHK(gf_exchange_rccl(c, c->gf_gsend, c->gf_ghost, true));
+    LQCHK(gauge_halo_links(U));
     LQCHK(plaquette_local_sum_device(U, c->gf_ghost, d_sum));
     return comm_allreduce(c, d_sum, 1);
 }

@@ -498,7 +498,7 @@ struct Tunables {
                               // max |row2 - conj(row0 x row1)| past the 12-real gate (1e-14) within ~280 link updates; 0 = the reference's literal update
     int staple_recon = 1;     // staple sweep on a field whose links are known to be on the group: rows 0, 1 are loaded, row 2 is rebuilt (2/3 of the L2 -> L1 bytes)
     int staple_tile = 1;      // staple sweep (single GPU, links on the group, chunks of whole x-rows): the links of both parities of a chunk sit in LDS and every neighbour link
-                              // inside that (x, y) tile is read from there (md.hip gauge_force_kernel_tile); 0: every neighbour link through the L1 / L2 path
+                              // inside that (x, y) tile is read from there (staple.hip gauge_force_kernel_tile); 0: every neighbour link through the L1 / L2 path
     int md_remap = 1;         // staple sweep: workgroups follow the Dslash kernels' XCD-aware tile sweep (0: plain chunk order)
     int cg_defer_x = 1;       // fused CG: 2 = x is updated every SECOND iteration with both search directions (x += a_k p_k + a_{k+1} p_{k+1}, p ping-pongs
                               // between two buffers): 9 instead of 10 spinor passes per iteration on average, identical iterates; K = 3..8 (round 5; 288 GB of HBM make
@@ -544,7 +544,7 @@ struct Tunables {
                               // instead of the CG on the normal equations (0: the reference's form); same stopping rule for the same residual (actions.hip)
     int lazy_links = 0;       // 1: the per-direction call triples of the reference's U_update! / P_update! (lqcd_link_exp -> lqcd_link_mul -> lqcd_link_copy,
                               // lqcd_link_staple -> lqcd_link_mul -> lqcd_link_add_ta) are recorded and run as ONE fused launch each, four completed triples of one
-                              // update as one four-direction launch (md.hip "lazy link triples"); 0: every call launches its own kernel.  The temporaries of a
+                              // update as one four-direction launch (links.hip "lazy link triples"); 0: every call launches its own kernel.  The temporaries of a
                               // completed fused triple are never written, so the plain C ABI is EAGER by default (every field holds what the call says it does);
                               // the Julia and Python bindings, whose callers hand the temporaries back to their pool unread, switch it on when they create a
                               // context
@@ -582,7 +582,7 @@ struct Tunables {
                               // scalar-addressing Wilson kernel: 896 B/site moved instead of 960, results equal to the 18-real kernel's to fp64 rounding; 0: always 18 reals
 };
 
-// Recorded single-direction link operations of one context (md.hip "lazy link triples").  A record holds raw handles: every entry point that
+// Recorded single-direction link operations of one context (links.hip "lazy link triples").  A record holds raw handles: every entry point that
 // reads, writes or destroys a gauge-shaped field runs the records first (links_flush), so none outlives a field it names.
 struct LinkRef {
     lqcd_gauge_s* g = nullptr;
@@ -608,14 +608,14 @@ struct LazyLinks {
     // links or writes the momenta in between, adds its step to it (runMD_QPQ_sw!'s back-to-back half steps, standardMD.jl:146-166)
     bool has_pend = false;
     Done pend = {0, nullptr, 0, 0.0, nullptr, 0.0};
-    // ... and a complete momentum update F += a TA(-(b/6) G staples) in front of it: the two run as one sweep (lazy_merge = 2, md.hip staple_force_expu)
+    // ... and a complete momentum update F += a TA(-(b/6) G staples) in front of it: the two run as one sweep (lazy_merge = 2, staple.hip staple_force_expu)
     bool has_pp = false;
     Done pp = {0, nullptr, 0, 0.0, nullptr, 0.0};
     bool busy() const { return kind != 0 || has_pend || has_pp || !done.empty(); }
 };
 constexpr int PIPE_CTR_WORDS = 10 * 32;          // the context's counter block (pipe_ctr): 8 per-XCD queue heads + 1 exit counter of the persistent stencil
 constexpr int PIPE_CTR_RED_WORD = 8 * 32 + 16;   // kernel, 128 B apart; two more words of the exit counter's line: the exterior's reduction ticket (stencil.hip) ...
-constexpr int PIPE_CTR_NOTPROJ_WORD = 8 * 32 + 24;   // ... and the "some link was not projected" flag of the link updates (md.hip)
+constexpr int PIPE_CTR_NOTPROJ_WORD = 8 * 32 + 24;   // ... and the "some link was not projected" flag of the link updates (gauge_staple.h launch_with_notproj_flag)
 
 
 
@@ -788,10 +788,10 @@ struct lqcd_ctx_s {
     // fermion-force halos (force.hip): full X and Y spinors of the lower face, allocated on first use
     double2* force_send[4] = {}, *force_recv[4] = {};
     int force_ncomp = 0;
-    // staple-force halos (md.hip): forward ghost links (+ their send buffer) and the lower-staple faces, allocated on first use
+    // staple-force halos (staple.hip): forward ghost links (+ their send buffer) and the lower-staple faces, allocated on first use
     double2* gf_ghost[4] = {}, *gf_gsend[4] = {}, *gf_wsend[4] = {}, *gf_wrecv[4] = {};
-    lqcd_gauge_s* stout_tmp[2] = {};    // W = U A and the N matrices of the stout back-propagation (md.hip), created on first use
-    double2* gauge_spare = nullptr;     // second link buffer of the fused momentum + link update (md.hip staple_force_expu), allocated on first use
+    lqcd_gauge_s* stout_tmp[2] = {};    // W = U A and the N matrices of the stout back-propagation (stout.hip), created on first use
+    double2* gauge_spare = nullptr;     // second link buffer of the fused momentum + link update (staple.hip staple_force_expu), allocated on first use
     double2* flow_x = nullptr;          // gradient flow (flow.hip): the RK3 accumulator, gauge-shaped, allocated on first use
     double* flow_partial = nullptr;     // ... block partials of the flow observables
     size_t flow_partial_n = 0;
@@ -825,7 +825,7 @@ struct lqcd_ctx_s {
     lqcd::Tunables tun;
     void* cg_session = nullptr;   // open timing session of lqcd_cg_session_* (ops.hip), if any
     int num_cu = 256;
-    lqcd::LazyLinks lazy;         // recorded single-direction link operations (md.hip)
+    lqcd::LazyLinks lazy;         // recorded single-direction link operations (links.hip)
     bool has_waiting_pack = false;   // folded halo schedule: the pack launch for the next application waits for the reduction it shares a launch with (apply.hip, blas.hip)
     void* waiting_pack = nullptr;    // its StencilCall (owned)
     // destroy calls from another thread than the context's own (a garbage collector's finalizer thread): a gauge-shaped field that recorded link
@@ -1096,7 +1096,7 @@ int gauge_ensure_recon12d(lqcd_gauge_s* g);  // (re)builds the "12 + delta" copy
 int plaquette_local_sum(lqcd_gauge_s* g, const double2* const ghost[4], double* sum);
 int gauge_pack_face(lqcd_gauge_s* g, int mu, double2* dst);
 
-// md.hip: run every recorded / deferred single-direction link operation of the context now (no-op when there is none)
+// links.hip: run every recorded / deferred single-direction link operation of the context now (no-op when there is none)
 int links_flush(lqcd_ctx_s* c);
 bool ctx_park_gauge(lqcd_gauge_s* g);      // capi.hip: true = called from a foreign thread while the context records link operations: parked, the caller must not touch it
 int ctx_drain_parked(lqcd_ctx_s* c);       // frees what foreign threads parked (called on the context's thread)

@@ -1738,7 +1738,7 @@ __global__ __launch_bounds__(UB) void ms_update_all(const double* __restrict__ s
 // (for sigma_j >= 0 every |zeta_j| <= 1, so the shifted residuals zeta_j r are then below eps as well).
 extern "C" int lqcd_solve_multishift_cg(lqcd_op_t op, lqcd_spinor_t x0, lqcd_spinor_t* xs, lqcd_spinor_t b, const double* sigma, int ns,
                                         double eps, int maxiter, int* iters, double* final_rr) {
-    LQCHK(lqcd::links_flush_of(op));      // recorded single-direction link operations run first (md.hip)
+    LQCHK(lqcd::links_flush_of(op));      // recorded single-direction link operations run first (links.hip)
     ARGCHK(op && b && ns >= 0 && ns <= 1024 && (ns == 0 || (xs && sigma)), "lqcd_solve_multishift_cg: null argument or more than 1024 shifts");
     ARGCHK(b->ctx == op->ctx && b->kind == op->kind && b->subset == LQCD_FULL, "lqcd_solve_multishift_cg: b must be a FULL spinor of the operator");
     for (int j = 0; j < ns; j++) {

@@ -53,7 +53,7 @@ class Lattice:
         self.set_param("lazy_links", 1)
 
     # The per-direction call triples of the reference's U_update! / P_update! (AbstractMD.jl:91-93, 108-110) are recorded and fused BELOW the C ABI
-    # (csrc/md.hip "lazy link triples", tunable lazy_links); this binding makes one stateless call per generic.  The three attributes below only
+    # (csrc/links.hip "lazy link triples", tunable lazy_links); this binding makes one stateless call per generic.  The three attributes below only
     # expose the library's state to the tests.
     @property
     def lazy_links(self):
@@ -629,7 +629,7 @@ class DdagD_operator:
 
 def _mul_links(C_, A, B):
     """mul!(W, expU, U[mu]) / mul!(temp1, U[mu], dSdUmu) (AbstractMD.jl:92,109): 3x3 products site by site (second call of a lazy triple: the
-    library records it, csrc/md.hip)."""
+    library records it, csrc/links.hip)."""
     if isinstance(A, AdjointLinkView):
         check(_l.lib().lqcd_link_mul_adj(C_.field._h, C_.slot, A.field._h, A.slot, B.field._h, B.slot))
         return C_
@@ -913,7 +913,7 @@ def fermion_force_(UdSfdU, D, X, Y, scale=1.0, accumulate=False):
 # ------------------------------------------------------------------------------------ gauge side of the MD step
 def substitute_U_(dst, src):
     """substitute_U!(Uold, U) (standardHMC.jl:45) on the Vector of link fields, substitute_U!(U[mu], W) (AbstractMD.jl:93) on one (third call of
-    the U_update! triple: the library turns exptU! -> mul! -> substitute_U! into one pass, csrc/md.hip)."""
+    the U_update! triple: the library turns exptU! -> mul! -> substitute_U! into one pass, csrc/links.hip)."""
     if isinstance(dst, LinkView):
         check(_l.lib().lqcd_link_copy(dst.field._h, dst.slot, src.field._h, src.slot))
         return dst

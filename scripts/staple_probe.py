@@ -1,5 +1,5 @@
 """Time of one Sexton-Weingarten block U_update! P_update! U_update! (standardMD.jl:150-152) at 32^3x64: the one-sweep momentum + link update
-(md.hip staple_force_expu) + the merged half steps.  usage: staple_probe.py [blocks] [--set key=value ...]"""
+(staple.hip staple_force_expu) + the merged half steps.  usage: staple_probe.py [blocks] [--set key=value ...]"""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import latticeqcd_jl_amd as lq

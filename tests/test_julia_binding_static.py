@@ -259,7 +259,7 @@ def test_domainwall_operator_of_universe_jl_resolves():
 
 def test_binding_keeps_no_module_level_mutable_state():
     """"no global mutable state outside the context handle".  Module-level `const X = Ref(...)`, `Dict(...)`, `Any[]` ... would be
-    shared by every lattice of the process (round 3's lazy-link record was); the lazy fusion now lives in the library's context (csrc/md.hip) and
+    shared by every lattice of the process (round 3's lazy-link record was); the lazy fusion now lives in the library's context (csrc/links.hip) and
     every link generic of the binding is one ccall."""
     text = binding_text()
     for m in re.finditer(r"(?m)^const\s+(\w+)\s*=\s*(.+)$", text):
