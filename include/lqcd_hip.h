@@ -103,7 +103,11 @@ int lqcd_ctx_sync(lqcd_ctx_t ctx);
  * buffers itself -- no exterior kernel, for every operator and both precisions; read-only halo_fold_active), cg_persist (1 [default]: a staggered CG on an unpartitioned lattice of
  * at most 256 chunks of 64 sites runs as ONE launch -- initial residual and all iterations, two grid-wide synchronisations per iteration, every wait bounded: if the workgroups are not all resident (a busy GPU) x is left untouched, the solve is
  * repeated by the launch chain and the key drops to 0; 0: the launch chain; 2: test hook that forces that fall-back), cg_small (1 [default]: on an unpartitioned lattice with <= 1024 stencil workgroups the two reduction launches of a fused CG
- * iteration are folded into the prologues of the kernels that consume them -- 3 dependent launches instead of 5, identical iterates), clover_fused (1 [default]: A x in the epilogue of the split kernel), clover_transport (1: partitioned-lattice
+ * iteration are folded into the prologues of the kernels that consume them -- 3 dependent launches instead of 5, identical iterates), cg_tgauge (1 [default]: the Wilson D^+D CG -- r = 1, no clover term,
+ * unpartitioned lattice of more than 1024 stencil workgroups, 12-real links active, scalar-addressing kernel -- iterates in temporal gauge: x0 and b are colour-rotated by G(x, t) = U_t(x, 0) ... U_t(x, t - 1),
+ * the stencils read a rotated 12-real copy of the links, cached per version of the field, and skip the time-like links below the last time slice (they are unit matrices), and x is rotated back on exit; the
+ * iterates equal the unrotated ones to rounding, b is not written; the copy must pass the 1e-14 gates of the 12-real links, else the solve runs unrotated; 0: off; 2: on small lattices too [tests];
+ * read-only tgauge_active: the last CG ran rotated.  An open CG session fails at its next lqcd_cg_session_iterate if the gauge field was changed under it), clover_fused (1 [default]: A x in the epilogue of the split kernel), clover_transport (1: partitioned-lattice
  * construction of the clover term / force also on one rank);
  * partitioned lattices: halo_merge (1 [default]: one message per peer when both faces go to the same rank), halo_stream_mode
  * (-1 [default]: time the four schedules of the halo exchange once -- collectively: every rank adopts the schedule with the smallest time summed over

@@ -166,7 +166,7 @@ extern "C" int lqcd_bench_cg(lqcd_op_t op, lqcd_spinor_t x, lqcd_spinor_t b, int
         if (e != hipSuccess && st == LQCD_OK) st = hip_fail(e, "bench_cg timing", __FILE__, __LINE__);
         *ms_per_iter = (double)t / niter;
     }
-    if (st == LQCD_OK) st = cg_flush_x(op, x, w);
+    { const int fs = cg_finish(op, x, w, st == LQCD_OK); if (st == LQCD_OK) st = fs; }
     (void)hipStreamSynchronize(c->stream);
     cg_work_put(w);
     return st;
@@ -187,6 +187,7 @@ extern "C" int lqcd_cg_session_begin(lqcd_op_t op, lqcd_spinor_t x, lqcd_spinor_
     double rr;
     if (st == LQCD_OK) st = cg_setup(op, x, b, w, -1.0, &rr);
     if (st != LQCD_OK) {
+        (void)cg_finish(op, x, w, false);      // (a set-up that failed behind its rotation of x)
         cg_work_put(w);
         delete ses;
         return st;
@@ -200,6 +201,10 @@ extern "C" int lqcd_cg_session_iterate(lqcd_op_t op, int n) {
     LQCHK(lqcd::links_flush_of(op));      // recorded single-direction link operations run first (links.hip)
     ARGCHK(op && op->ctx->cg_session && static_cast<CgSession*>(op->ctx->cg_session)->op == op, "lqcd_cg_session_iterate: no open session for this operator");
     CgSession* ses = static_cast<CgSession*>(op->ctx->cg_session);
+    if (cg_gauge_moved(op, ses->w)) {
+        set_error("lqcd_cg_session_iterate: the gauge field changed under the open session (it iterates in the temporal gauge of the links it was begun on): end it and begin a new one");
+        return LQCD_ERR_ARG;
+    }
     for (int i = 0; i < n; i++) LQCHK(cg_enqueue_iteration(op, ses->x, ses->w));
     HIPCHK(hipStreamSynchronize(op->ctx->stream));
     return LQCD_OK;
@@ -208,7 +213,7 @@ extern "C" int lqcd_cg_session_end(lqcd_op_t op) {
     ARGCHK(op && op->ctx->cg_session && static_cast<CgSession*>(op->ctx->cg_session)->op == op, "lqcd_cg_session_end: no open session for this operator");
     CgSession* ses = static_cast<CgSession*>(op->ctx->cg_session);
     CgWork& w = ses->w;
-    const int st = cg_flush_x(op, ses->x, w);       // a pending deferred x update; its status is the status of the session
+    const int st = cg_finish(op, ses->x, w);       // a pending deferred x update (and x back from temporal gauge); its status is the status of the session
     (void)hipStreamSynchronize(op->ctx->stream);
     cg_work_put(w);
     delete ses;

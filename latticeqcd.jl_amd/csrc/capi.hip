@@ -279,7 +279,7 @@ extern "C" int lqcd_ctx_destroy(lqcd_ctx_t c) {
     }
     for (void* b : c->mix_buf) (void)hipFree(b);
     (void)hipFree(c->clover_q[0]); (void)hipFree(c->clover_q[1]);
-    for (lqcd_gauge_s*& t : c->stout_tmp) if (t) { (void)hipFree(t->data); (void)hipFree(t->data12); (void)hipFree(t->data12d); delete t; t = nullptr; }
+    for (lqcd_gauge_s*& t : c->stout_tmp) if (t) { (void)hipFree(t->data); (void)hipFree(t->data12); (void)hipFree(t->data12d); (void)hipFree(t->data12t); (void)hipFree(t->gfix); delete t; t = nullptr; }
     (void)hipFree(c->gauge_spare);
     (void)hipFree(c->flow_x); (void)hipFree(c->flow_partial); (void)hipFree(c->flow_tab);
     (void)hipFree(c->hb_tab);
@@ -332,6 +332,8 @@ static int* param_ptr(lqcd_ctx_s* c, const char* key) {
     if (!strcmp(key, "halo_stream_mode")) return &c->tun.halo_stream_mode;
     if (!strcmp(key, "cg_skip_done")) return &c->tun.cg_skip_done;
     if (!strcmp(key, "cg_small")) return &c->tun.cg_small;
+    if (!strcmp(key, "cg_tgauge")) return &c->tun.cg_tgauge;
+    if (!strcmp(key, "tgauge_active")) return &c->tun.tgauge_active;
     if (!strcmp(key, "cg_persist")) return &c->tun.cg_persist;
     if (!strcmp(key, "md_remap")) return &c->tun.md_remap;
     if (!strcmp(key, "staple_recon")) return &c->tun.staple_recon;

@@ -279,6 +279,8 @@ int gauge_destroy_now(lqcd_gauge_s* g) {
     (void)hipFree(g->data);
     (void)hipFree(g->data12);
     (void)hipFree(g->data12d);
+    (void)hipFree(g->data12t);
+    (void)hipFree(g->gfix);
     delete g;
     return LQCD_OK;
 }
@@ -581,6 +583,162 @@ int gauge_ensure_recon12d(lqcd_gauge_s* g) {
     memcpy(&dev, &bits, sizeof(dev));
     g->delta_ok = dev <= 1e-9;
     g->version12d = g->version;
+    return LQCD_OK;
+}
+
+// ------------------------------------------------------------------ temporal gauge for the Wilson CG
+// G(x, 0) = 1, G(x, t + 1) = G(x, t) U_t(x, t) and U'_mu(n) = G(n) U_mu(n) G(n + mu)^+ make every time-like link the unit matrix except on the last time
+// slice (the seam), and D[U'] (G psi) = G D[U] psi exactly: the CG on (U', G b, G x0) produces G x_k.  Its stencils then skip the time-like links below the seam.
+__device__ inline void tg_row2(cd (&u)[9]) {      // row 2 = conj(row 0 x row 1): the fma sequence of the stencils' recon_row2 (stencil_common.h)
+#pragma unroll
+    for (int b = 0; b < 3; b++) {
+        const int b1 = (b + 1) % 3, b2 = (b + 2) % 3;
+        const cd a = u[b1], bb = u[3 + b2], c = u[b2], d = u[3 + b1];
+        double wr = a.re * bb.re;
+        wr = fma(-a.im, bb.im, wr); wr = fma(-c.re, d.re, wr); wr = fma(c.im, d.im, wr);
+        double wi = a.re * bb.im;
+        wi = fma(a.im, bb.re, wi); wi = fma(-c.re, d.im, wi); wi = fma(-c.im, d.re, wi);
+        u[6 + b] = mk(wr, -wi);
+    }
+}
+__device__ inline void tg_load12(cd (&u)[9], const double2* __restrict__ src) {      // a 12-real link as the stencils see it
+#pragma unroll
+    for (int e = 0; e < 6; e++) u[e] = ld(src + (size_t)e * 64);
+    tg_row2(u);
+}
+// One thread per spatial site (x = 2 xh + q, y, z): G along its time line, t = 0 .. T - 1 in order.  G is put back on the group at every step (Gram-Schmidt on
+// rows 0, 1; row 2 = conj(row 0 x row 1)): without that the product drifts off SU(3) with T and the rotated links fail the 12-real gate at T = 64.
+__global__ __launch_bounds__(64) void tgauge_scan(Geom g, const double2* __restrict__ u12, double2* __restrict__ gf) {
+    const int plane = g.XH * g.L[1] * g.L[2];
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= 2 * plane) return;
+    const int q = s >= plane ? 1 : 0, rem = s - q * plane;
+    const int yz = fdiv(rem, g.dXH), z = fdiv(yz, g.dL1), y = yz - z * g.L[1];
+    cd G[9];
+#pragma unroll
+    for (int e = 0; e < 9; e++) G[e] = mk((e == 0 || e == 4 || e == 8) ? 1.0 : 0.0, 0.0);
+    for (int t = 0; t < g.L[3]; t++) {
+        const int p = (q + y + z + t) & 1, i = rem + plane * t;      // checkerboard index of (x, y, z, t): xh + XH (y + L1 (z + L2 t))
+        double2* dst = gf + gfix_off(g, p, i);
+#pragma unroll
+        for (int e = 0; e < 9; e++) st(dst + (size_t)e * 64, G[e]);
+        if (t == g.L[3] - 1) break;
+        cd u[9], w[9];
+        tg_load12(u, u12 + glink12_off(g, p, 3, i));
+#pragma unroll
+        for (int a = 0; a < 2; a++)
+#pragma unroll
+            for (int b = 0; b < 3; b++) {
+                cd acc = cmul(G[a * 3], u[b]);
+                cfma(acc, G[a * 3 + 1], u[3 + b]);
+                cfma(acc, G[a * 3 + 2], u[6 + b]);
+                w[a * 3 + b] = acc;
+            }
+        double n0 = 0.0;
+#pragma unroll
+        for (int b = 0; b < 3; b++) { n0 = fma(w[b].re, w[b].re, n0); n0 = fma(w[b].im, w[b].im, n0); }
+        const double i0 = 1.0 / sqrt(n0);
+#pragma unroll
+        for (int b = 0; b < 3; b++) w[b] = i0 * w[b];
+        cd d = mk(0.0, 0.0);      // <row 0, row 1>
+#pragma unroll
+        for (int b = 0; b < 3; b++) cfma_conj(d, w[b], w[3 + b]);
+        double n1 = 0.0;
+#pragma unroll
+        for (int b = 0; b < 3; b++) {
+            w[3 + b] = w[3 + b] - cmul(d, w[b]);
+            n1 = fma(w[3 + b].re, w[3 + b].re, n1); n1 = fma(w[3 + b].im, w[3 + b].im, n1);
+        }
+        const double i1 = 1.0 / sqrt(n1);
+#pragma unroll
+        for (int b = 0; b < 3; b++) w[3 + b] = i1 * w[3 + b];
+        tg_row2(w);
+#pragma unroll
+        for (int e = 0; e < 9; e++) G[e] = w[e];
+    }
+}
+// U' = G(n) U G(n + mu)^+, rows 0, 1 at the offsets of the 12-real copy; lane = site, blockIdx.y = (parity, mu) like gauge_compress12.  The time-like links below
+// the seam are measured against the unit matrix and stored as exact unit matrices: a 12-real kernel that does not skip them multiplies by 1 and 0 and gets the bits
+// of one that does.  *maxdev: the larger of max |row 2 - conj(row 0 x row 1)| of U' and max |U'_t - 1| below the seam (bit pattern, see gauge_compress12).
+__global__ __launch_bounds__(256) void tgauge_rotate_links(Geom g, const double2* __restrict__ u12, const double2* __restrict__ gf, double2* __restrict__ dst, unsigned long long* maxdev) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, p = blockIdx.y >> 2, mu = blockIdx.y & 3;
+    double dev = 0.0;
+    if (i < g.Vh) {
+        int c[4];
+        cb_to_coords(g, p, i, c);
+        const bool below = mu == 3 && c[3] != g.L[3] - 1;
+        c[mu] = c[mu] == g.L[mu] - 1 ? 0 : c[mu] + 1;
+        const int j = coords_to_cb(g, c);
+        cd u[9], G[9], H[9], w[9], v[9];
+        tg_load12(u, u12 + glink12_off(g, p, mu, i));
+        const double2* gp = gf + gfix_off(g, p, i);
+        const double2* hp = gf + gfix_off(g, 1 - p, j);
+#pragma unroll
+        for (int e = 0; e < 9; e++) { G[e] = ld(gp + (size_t)e * 64); H[e] = ld(hp + (size_t)e * 64); }
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+#pragma unroll
+            for (int b = 0; b < 3; b++) {      // w = U H^+
+                cd acc = mk(0.0, 0.0);
+#pragma unroll
+                for (int k = 0; k < 3; k++) cfma_conj(acc, H[b * 3 + k], u[a * 3 + k]);
+                w[a * 3 + b] = acc;
+            }
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+#pragma unroll
+            for (int b = 0; b < 3; b++) {      // v = G w
+                cd acc = mk(0.0, 0.0);
+#pragma unroll
+                for (int k = 0; k < 3; k++) cfma(acc, G[a * 3 + k], w[k * 3 + b]);
+                v[a * 3 + b] = acc;
+            }
+        cd ref[9];
+        if (below) {
+#pragma unroll
+            for (int e = 0; e < 9; e++) ref[e] = mk((e == 0 || e == 4 || e == 8) ? 1.0 : 0.0, 0.0);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 6; e++) ref[e] = v[e];
+            tg_row2(ref);
+        }
+#pragma unroll
+        for (int e = 0; e < 9; e++) {
+            const double d1 = fabs(v[e].re - ref[e].re), d2 = fabs(v[e].im - ref[e].im);
+            dev = (d1 <= 1e300 && d2 <= 1e300) ? fmax(dev, fmax(d1, d2)) : 1e300;
+        }
+        const size_t d_o = glink12_off(g, p, mu, i);
+#pragma unroll
+        for (int e = 0; e < 6; e++) st(dst + d_o + (size_t)e * 64, ref[e]);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) dev = fmax(dev, __shfl_down(dev, off, 64));
+    if ((threadIdx.x & 63) == 0 && dev > 0.0) atomicMax(maxdev, (unsigned long long)__double_as_longlong(dev));
+}
+
+int gauge_ensure_tgauge(lqcd_gauge_s* g) {
+    LQCHK(gauge_ensure_recon12(g));
+    if (g->version12t == g->version && g->data12t && g->gfix) return LQCD_OK;
+    lqcd_ctx_s* c = g->ctx;
+    g->tgauge_ok = false;
+    if (!g->recon_ok || c->geom.part[0] || c->geom.part[1] || c->geom.part[2] || c->geom.part[3] || c->geom.L[3] < 2) return LQCD_OK;
+    HIPCHK(hipSetDevice(c->device));
+    if (!g->data12t) HIPCHK(hipMalloc((void**)&g->data12t, gauge12_elems(c->geom) * sizeof(double2)));
+    if (!g->gfix) HIPCHK(hipMalloc((void**)&g->gfix, (size_t)2 * c->geom.nch * 9 * 64 * sizeof(double2)));
+    unsigned long long* d_dev = (unsigned long long*)(c->d_scal + SCAL_DOUBLES - 9);
+    HIPCHK(hipMemsetAsync(d_dev, 0, sizeof(unsigned long long), c->stream));
+    const int nline = 2 * c->geom.XH * c->geom.L[1] * c->geom.L[2];
+    hipLaunchKernelGGL(tgauge_scan, dim3((nline + 63) / 64), dim3(64), 0, c->stream, c->geom, g->data12, g->gfix);
+    hipLaunchKernelGGL(tgauge_rotate_links, dim3((c->geom.Vh + 255) / 256, 8), dim3(256), 0, c->stream, c->geom, g->data12, g->gfix, g->data12t, d_dev);
+    HIPCHK(hipGetLastError());
+    unsigned long long bits = 0;
+    HIPCHK(hipMemcpyAsync(&bits, d_dev, sizeof(bits), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    double dev;
+    memcpy(&dev, &bits, sizeof(dev));
+    g->tgauge_ok = dev <= 1e-14;
+    g->tgauge_dev = dev;
+    g->version12t = g->version;
     return LQCD_OK;
 }
 

@@ -109,6 +109,9 @@ __host__ __device__ inline size_t glink_off(const Geom& g, int p, int mu, int i)
 __host__ __device__ inline size_t glink12_off(const Geom& g, int p, int mu, int i) {   // 12-real copy: [parity][chunk][mu][6][64]
     return ((((size_t)p * g.nch + (size_t)(i >> 6)) * 4 + mu) * 6) * 64 + (i & 63);
 }
+__host__ __device__ inline size_t gfix_off(const Geom& g, int p, int i) {   // gauge-transformation field G (temporal gauge, fields.hip): [parity][chunk][9][64]
+    return (((size_t)p * g.nch + (size_t)(i >> 6)) * 9) * 64 + (i & 63);
+}
 __host__ __device__ inline size_t gauge12_elems(const Geom& g) { return (size_t)2 * g.nch * 24 * 64; }
 __host__ __device__ inline int glink_stride(const Geom& g) {   // distance between consecutive components of one link
 #if LQCD_GAUGE_AOSOA
@@ -509,6 +512,10 @@ struct Tunables {
                               // synchronisations per iteration instead of three dependent launches; 0: the cg_small launch chain
     int cg_small = 1;         // fused CG on an unpartitioned lattice with <= 1024 stencil workgroups: the two reduction launches of an iteration are folded
                               // into the prologues of the kernels that consume them (3 dependent launches per iteration instead of 5)
+    int cg_tgauge = 1;        // Wilson CG (r = 1, no clover term, unpartitioned, 12-real links, scalar-addressing kernel): the solve runs in temporal gauge on rotated vectors and
+                              // its stencils skip the time-like links below the seam.  0: off; 1 (default): beyond the cg_small regime (more than 1024 stencil workgroups);
+                              // 2: whenever admissible (tests)
+    int tgauge_active = 0;    // read-only: 1 if the last CG set up through cg_setup ran in temporal gauge
     int cg_skip_done = 1;     // fused CG: the first Dslash of an iteration checks the convergence flag as well (0: only the second does)
     int clover_transport = 0; // 1: build the clover sums by the plaquette-transport passes also on an unpartitioned lattice (tests)
     int stag_both = 0;            // 1: staggered split kernel issues the loads of both hops of a direction back to back (unpartitioned lattices)
@@ -851,6 +858,14 @@ struct lqcd_gauge_s {
     double2* data12d = nullptr;
     uint64_t version12d = 0;
     bool delta_ok = false;
+    // temporal-gauge copy for the Wilson CG (fields.hip gauge_ensure_tgauge): gfix = G(n) with G(x, 0) = 1, G(x, t + 1) = G(x, t) U_t(x, t), all 18 reals,
+    // [parity][chunk][9][64]; data12t = rows 0, 1 of U'_mu(n) = G(n) U_mu(n) G(n + mu)^+ in the layout of data12, the time-like links below the seam t = T - 1
+    // stored as exact unit matrices (measured to be the unit matrix to 1e-14 first).  D[U'] (G psi) = G D[U] psi: the same operator in another basis.
+    double2* data12t = nullptr;
+    double2* gfix = nullptr;
+    uint64_t version12t = 0;
+    bool tgauge_ok = false;      // rows 0, 1 of every U' rebuild its row 2 to 1e-14 and every time-like U' below the seam is the unit matrix to 1e-14
+    double tgauge_dev = 0.0;     // the larger of those two deviations
     uint64_t unitary_version = 0;  // version of `data` whose links are all known to be on the group to rounding (generated on it, measured by the
                                    // 12-real pass, or projected by the link update): kernels may then rebuild row 2 instead of loading it
 };
@@ -975,6 +990,8 @@ struct StencilCall {
     int alpha_n = 0;
     double* scal_w = nullptr;     // the device scalar block, writable: block 0 records pq, alpha and the rr this iteration started from
     const double2* gauge12 = nullptr;  // compressed links (fp64 build, Wilson r = 1 split kernel) or nullptr
+    const double2* gauge12t = nullptr; // temporal-gauge copy of the 12-real links (lqcd_gauge_s::data12t; the Wilson CG on rotated vectors): read in place of gauge12; the
+                                       // scalar-addressing kernel's TG instances skip the time-like links below the seam, every other 12-real kernel multiplies by their unit matrices
     const void* gauge16 = nullptr;     // prec == 2 only: the int16 fixed-point pair copy of the 12-real links (stencil_pair32.hip ldx16); the kernel then reads it instead of gauge12
     int gauge12_delta = 0;        // 1: gauge12 is the 8-word "12 + delta" copy (lqcd_gauge_s::data12d); only the scalar-addressing Wilson kernel reads it, every
                                   // other launch of the call falls back to the 18 stored reals
@@ -1048,7 +1065,7 @@ int flush_waiting_pack(lqcd_ctx_s* c);       // apply.hip
 int halo_schedule_settle(lqcd_op_s* op);   // partitioned context with halo_stream_mode = -1: run the one-off schedule timing now (apply.hip)
 int op_refresh_clover(lqcd_op_s* op);   // rebuilds A when the links moved; clover_version follows only a successful build
 void apply_bc(lqcd_ctx_s* c, const int bc[4]);
-int op_apply_async(lqcd_op_s* op, lqcd_spinor_s* out, lqcd_spinor_s* in, int dagger, double* norm_partial, const double* skip_flag = nullptr);
+int op_apply_async(lqcd_op_s* op, lqcd_spinor_s* out, lqcd_spinor_s* in, int dagger, double* norm_partial, const double* skip_flag = nullptr, const double2* gauge12t = nullptr);
 int cg_run(lqcd_op_s* op, lqcd_spinor_s* x, lqcd_spinor_s* b, double eps, int maxiter, bool fixed, int* iters, double* final_rr);
 bool any_partitioned(lqcd_ctx_s* c);
 bool halo_fold_applies(lqcd_ctx_s* c, int kind, double r, int parity_mode, int prec, bool clover);   // the folded one-stream schedule runs for such a call (stencil.hip)
@@ -1093,6 +1110,9 @@ int clover_force(lqcd_ctx_s* c, const lqcd_gauge_s* U, lqcd_gauge_s* out, lqcd_s
 double2* spinor_block(lqcd_spinor_s* s, int p);
 int gauge_ensure_recon12(lqcd_gauge_s* g);   // (re)builds the 12-real copy if the field changed; sets g->recon_ok
 int gauge_ensure_recon12d(lqcd_gauge_s* g);  // (re)builds the "12 + delta" copy; sets g->delta_ok
+int gauge_ensure_tgauge(lqcd_gauge_s* g);    // (re)builds G and the temporal-gauge copy of the 12-real links if the field changed; sets g->tgauge_ok
+int spinor_gauge_rotate(lqcd_ctx_s* c, const double2* gfix, double2* dst, const double2* src, int adjoint);   // solvers.hip: dst = G src / G^+ src on a full Wilson field (dst may be src)
+bool stencil_tgauge_applies(lqcd_ctx_s* c, int kind, double r, bool clover);   // stencil.hip: a full-lattice fp64 application with 12-real links would take the TG instances
 int plaquette_local_sum(lqcd_gauge_s* g, const double2* const ghost[4], double* sum);
 int gauge_pack_face(lqcd_gauge_s* g, int mu, double2* dst);
 

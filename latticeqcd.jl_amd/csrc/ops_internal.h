@@ -28,12 +28,21 @@ struct CgWork {
     int ring = 2;       // form 1: search-direction buffers in rotation (2: p, q; K > 2: p, q, more[0..K-3]; p_k lives in buffer k % K), fixed at cg_setup
     lqcd_spinor_s* more[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     lqcd_spinor_s* buf(int j) const { return j == 0 ? p : j == 1 ? q : more[j - 2]; }
+    // temporal gauge (decided once in cg_setup): x, r and the search directions are G times the caller's vectors and every stencil call of the iteration reads
+    // the rotated links; cg_finish rotates x back
+    bool tgauge = false;
+    const double2* links_t = nullptr;      // lqcd_gauge_s::data12t of the field version the solve was set up on
+    const double2* gfix = nullptr;
+    uint64_t gauge_version = 0;
 };
 int cg_work_get(lqcd_ctx_s* c, int kind, CgWork& w);      // the four work vectors of a solve from the context's scratch pool (the ring's extra buffers follow in cg_setup)
 void cg_work_put(CgWork& w);
 int cg_enqueue_iteration(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w);
 int cg_flush_x(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w);    // applies a pending deferred x update (end of a window that stopped on an even iteration)
 int cg_setup(lqcd_op_s* op, lqcd_spinor_s* x, lqcd_spinor_s* b, CgWork& w, double eps, double* rr0);
+// the one exit of a solve / window set up by cg_setup: the pending deferred x update (flush = false: the solve converged, x is complete) and, in temporal gauge, x <- G^+ x
+int cg_finish(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w, bool flush = true);
+bool cg_gauge_moved(lqcd_op_s* op, const CgWork& w);      // temporal gauge: the links changed since cg_setup (an open session must not go on)
 // cg_persist.hip: a staggered CG on a launch-bound lattice as ONE launch (initial residual included; the work vectors lend their storage)
 bool cg_persist_ok(lqcd_op_s* op);
 int cg_persist_run(lqcd_op_s* op, lqcd_spinor_s* x, lqcd_spinor_s* b, CgWork& w, double eps, int maxiter, int* iters, double* rr, bool* converged, bool* gave_up);

@@ -337,6 +337,39 @@ __global__ __launch_bounds__(UB) void redot_partial_kernel(const double2* __rest
 }
 
 
+// ---------------------------------------------------------------------------------- temporal gauge (fields.hip gauge_ensure_tgauge)
+// psi <- G psi / G^+ psi, colour rotation of a full Wilson field by the gauge-transformation field: one site per thread, [chunk][component][lane] rows of 1 KiB,
+// su3_mv's fma order.  dst may be src.
+template <bool ADJ>
+__global__ __launch_bounds__(UB) void spinor_gauge_rotate_kernel(Geom g, const double2* __restrict__ gf, double2* dst, const double2* src) {
+    const int i = blockIdx.x * UB + threadIdx.x, p = blockIdx.y;
+    if (i >= g.Vh) return;
+    const size_t so = (size_t)p * 12 * g.Vs + sp_off(12, i);
+    const int Ss = sp_stride(g);
+    cd G[9], in[12], out[12];
+    const double2* gp = gf + gfix_off(g, p, i);
+#pragma unroll
+    for (int e = 0; e < 9; e++) G[e] = ld(gp + (size_t)e * 64);
+#pragma unroll
+    for (int j = 0; j < 12; j++) in[j] = ld(src + so + (size_t)j * Ss);
+#pragma unroll
+    for (int sp = 0; sp < 4; sp++) {
+        cd h[3] = {in[3 * sp], in[3 * sp + 1], in[3 * sp + 2]}, chi[3];
+        su3_mv<ADJ>(chi, G, h);
+#pragma unroll
+        for (int cc = 0; cc < 3; cc++) out[3 * sp + cc] = chi[cc];
+    }
+#pragma unroll
+    for (int j = 0; j < 12; j++) st(dst + so + (size_t)j * Ss, out[j]);
+}
+int spinor_gauge_rotate(lqcd_ctx_s* c, const double2* gfix, double2* dst, const double2* src, int adjoint) {
+    const dim3 grid((c->geom.Vh + UB - 1) / UB, 2), block(UB);
+    if (adjoint) hipLaunchKernelGGL((spinor_gauge_rotate_kernel<true>), grid, block, 0, c->stream, c->geom, gfix, dst, src);
+    else hipLaunchKernelGGL((spinor_gauge_rotate_kernel<false>), grid, block, 0, c->stream, c->geom, gfix, dst, src);
+    HIPCHK(hipGetLastError());
+    return LQCD_OK;
+}
+
 // cg_small applies when the reductions are local (no communicator), at most 1024 block partials exist, and the stencil kernel in use
 // takes alpha from emit()'s argument (every variant but the hop-split ones)
 static bool cg_small_ok(lqcd_op_s* op, int nbs) {
@@ -401,9 +434,32 @@ int cg_flush_x(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
     return LQCD_OK;
 }
 
+int cg_finish(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w, bool flush) {
+    int st = flush ? cg_flush_x(op, x, w) : LQCD_OK;
+    if (w.tgauge) {      // (also behind a failed flush: the caller's x leaves the rotated basis on every path)
+        const int sr = spinor_gauge_rotate(op->ctx, w.gfix, x->data, x->data, 1);
+        if (st == LQCD_OK) st = sr;
+        w.tgauge = false;
+    }
+    return st;
+}
+bool cg_gauge_moved(lqcd_op_s* op, const CgWork& w) { return w.tgauge && (op->gauge->version != w.gauge_version || op->gauge->data12t != w.links_t); }
+
+// The solve runs in temporal gauge when: Wilson, r = 1, no clover term, unpartitioned lattice, the stencil launches of the iteration take the TG instances
+// (asked before anything is rotated), the rotated copy of this version of the links passed its gate, and the tunable cg_tgauge allows it -- 1: beyond the
+// cg_small regime only (below it an iteration is launch latency and the three rotations of a solve are pure cost), 2: whenever admissible.
+static bool cg_tgauge_wanted(lqcd_op_s* op) {
+    lqcd_ctx_s* c = op->ctx;
+    if (!c->tun.cg_tgauge || op->kind != LQCD_WILSON || op->r != 1.0 || op->csw != 0.0 || any_partitioned(c) || !c->local_peers.empty()) return false;
+    if (!stencil_tgauge_applies(c, op->kind, op->r, op_fused_clover(op))) return false;
+    if (c->tun.cg_tgauge < 2 && stencil_num_partials(c, op->kind, op->r, 2, 0, op_fused_clover(op)) <= 1024) return false;
+    return gauge_ensure_tgauge(op->gauge) == LQCD_OK && op->gauge->tgauge_ok;
+}
+
 int cg_enqueue_iteration(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
     lqcd_ctx_s* c = op->ctx;
     const size_t n = x->elems;
+    const double2* gt = w.tgauge ? w.links_t : nullptr;      // temporal gauge: every stencil call below reads the rotated links
     const int nbs_small = stencil_num_partials(c, op->kind, op->r, 2, 0, op_fused_clover(op));
     // the iteration form was fixed when the solve / session was set up (a tunable changed in between must not split a pending deferred update)
     const int form = w.form >= 0 ? w.form : ((c->tun.cg_fused >= 2 && c->tun.cg_small && cg_small_ok(op, nbs_small)) ? 2 : (cg_defers_x(op) ? 1 : 0));
@@ -412,10 +468,11 @@ int cg_enqueue_iteration(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
         // are folded into the prologues of their consumers -- 3 dependent launches per iteration instead of 5, identical iterates.
         double* part_a = c->d_partial;            // |D p|^2 block partials
         double* part_b = c->d_partial + 2048;     // |r|^2 block partials (the update-mode kernel reads part_a while its blocks write these)
-        LQCHK(op_apply_async(op, w.tmp, w.p, 0, part_a, c->tun.cg_skip_done ? c->d_scal : nullptr));
+        LQCHK(op_apply_async(op, w.tmp, w.p, 0, part_a, c->tun.cg_skip_done ? c->d_scal : nullptr, gt));
         apply_bc(c, op->bc);
         StencilCall s2;
         LQCHK(make_full_call(op, w.q, w.tmp, 1, s2));
+        s2.gauge12t = gt;
         s2.norm_partial = part_b;
         s2.upd_scal = c->d_scal;
         s2.upd[0] = spinor_block(w.r, 0);
@@ -451,6 +508,7 @@ int cg_enqueue_iteration(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
             apply_bc(c, op->bc);      // another operator of this context (other boundary signs) may have been applied since the last iteration of an open session
             StencilCall s1;
             LQCHK(make_full_call(op, w.tmp, pk, 0, s1));
+            s1.gauge12t = gt;
             s1.norm_partial = c->d_partial;
             s1.skip_flag = c->tun.cg_skip_done ? c->d_scal : nullptr;      // a no-op once the solve has converged inside a burst
             if (fr) s1.red_slot = S_PQ;
@@ -461,6 +519,7 @@ int cg_enqueue_iteration(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
         apply_bc(c, op->bc);
         StencilCall s2;
         LQCHK(make_full_call(op, po, w.tmp, 1, s2));          // update mode writes r only: `out` is a placeholder (the buffer that is dead until the p update)
+        s2.gauge12t = gt;
         s2.norm_partial = c->d_partial;
         if (fold) s2.scal_w = c->d_scal;
         s2.upd_scal = c->d_scal;
@@ -517,21 +576,21 @@ int cg_enqueue_iteration(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
     }
     const bool fuse = c->tun.cg_fused && !any_partitioned(c);
     // tmp = D p  (|tmp|^2 block partials fused into the stencil when the lattice is not partitioned)
-    LQCHK(op_apply_async(op, w.tmp, w.p, 0, fuse ? c->d_partial : nullptr));
+    LQCHK(op_apply_async(op, w.tmp, w.p, 0, fuse ? c->d_partial : nullptr, nullptr, gt));
     int nb;
     if (fuse) {
         nb = stencil_num_blocks(c, op->kind, op->r, 2, 0, op_fused_clover(op));
         LQCHK(reduce_to_slot(c, nb, 1, S_PQ, true));
-        LQCHK(op_apply_async(op, w.q, w.tmp, 1, nullptr));
+        LQCHK(op_apply_async(op, w.q, w.tmp, 1, nullptr, nullptr, gt));
     } else if (c->tun.cg_fused) {
         nb = stream_grid(c, n);
         hipLaunchKernelGGL(norm2_partial_kernel, dim3(nb), dim3(UB), 0, c->stream, w.tmp->data, n, c->d_partial);
         HIPCHK(hipGetLastError());
         LQCHK(reduce_to_slot(c, nb, 1, S_PQ, true));
-        LQCHK(op_apply_async(op, w.q, w.tmp, 1, nullptr));
+        LQCHK(op_apply_async(op, w.q, w.tmp, 1, nullptr, nullptr, gt));
     } else {
         // reference form: c1 = p . q
-        LQCHK(op_apply_async(op, w.q, w.tmp, 1, nullptr));
+        LQCHK(op_apply_async(op, w.q, w.tmp, 1, nullptr, nullptr, gt));
         nb = stream_grid(c, n);
         hipLaunchKernelGGL(redot_partial_kernel, dim3(nb), dim3(UB), 0, c->stream, w.p->data, w.q->data, n, c->d_partial);
         HIPCHK(hipGetLastError());
@@ -552,10 +611,18 @@ int cg_setup(lqcd_op_s* op, lqcd_spinor_s* x, lqcd_spinor_s* b, CgWork& w, doubl
     lqcd_ctx_s* c = op->ctx;
     const size_t n = x->elems;
     LQCHK(halo_schedule_settle(op));      // the iteration counts |.|^2 partials: the halo schedule (folded or not) is fixed from here on
+    // temporal gauge: x <- G x in place (cg_finish rotates it back), r = G b - D'^+ D' x without a write to b (it belongs to the caller)
+    w.tgauge = cg_tgauge_wanted(op);
+    c->tun.tgauge_active = w.tgauge ? 1 : 0;
+    w.links_t = w.tgauge ? op->gauge->data12t : nullptr;
+    w.gfix = w.tgauge ? op->gauge->gfix : nullptr;
+    w.gauge_version = op->gauge->version;
+    if (w.tgauge) LQCHK(spinor_gauge_rotate(c, w.gfix, x->data, x->data, 0));
     // r = b - D^+ D x ; p = r
-    LQCHK(op_apply_async(op, w.tmp, x, 0, nullptr));
-    LQCHK(op_apply_async(op, w.q, w.tmp, 1, nullptr));
-    HIPCHK(hipMemcpyAsync(w.r->data, b->data, n * sizeof(double2), hipMemcpyDeviceToDevice, c->stream));
+    LQCHK(op_apply_async(op, w.tmp, x, 0, nullptr, nullptr, w.links_t));
+    LQCHK(op_apply_async(op, w.q, w.tmp, 1, nullptr, nullptr, w.links_t));
+    if (w.tgauge) LQCHK(spinor_gauge_rotate(c, w.gfix, w.r->data, b->data, 0));
+    else HIPCHK(hipMemcpyAsync(w.r->data, b->data, n * sizeof(double2), hipMemcpyDeviceToDevice, c->stream));
     LQCHK(blas_axpy(c, -1.0, 0.0, w.q->data, w.r->data, n));
     HIPCHK(hipMemcpyAsync(w.p->data, w.r->data, n * sizeof(double2), hipMemcpyDeviceToDevice, c->stream));
     LQCHK(blas_norm2(c, w.r->data, n, rr0, true));
@@ -655,8 +722,9 @@ int cg_run(lqcd_op_s* op, lqcd_spinor_s* x, lqcd_spinor_s* b, double eps, int ma
     }
     if (gexec) (void)hipGraphExecDestroy(gexec);
     if (graph) (void)hipGraphDestroy(graph);
-    if (st == LQCD_OK && !converged && !one_launch) {          // a window / an exhausted solve that stopped on an even iteration: complete x
-        st = cg_flush_x(op, x, w);
+    if (!one_launch && (w.tgauge || (st == LQCD_OK && !converged))) {      // a window / an exhausted solve that stopped on an even iteration: complete x; temporal gauge: x back to the caller's basis
+        const int fs = cg_finish(op, x, w, st == LQCD_OK && !converged);
+        if (st == LQCD_OK) st = fs;
         if (st == LQCD_OK) { hipError_t e = hipStreamSynchronize(c->stream); if (e != hipSuccess) st = hip_fail(e, "cg flush", __FILE__, __LINE__); }
     }
     cg_work_put(w);

@@ -769,7 +769,10 @@ __device__ inline void fold_unit_link(cd (&u)[9], bool face) {      // (called w
     }
 }
 
-template <int MU, bool DAG, bool R12, bool NTB, bool DOT = false, bool DELTA = false, bool DW5 = false, bool FOLD = false, bool CINV = false>
+// TG (plain fp64 12-real instances only): the links are the temporal-gauge copy (lqcd_gauge_s::data12t) -- a time-like link is the unit matrix unless its hop crosses
+// the seam t = T - 1 -> 0, which is what s.wf / s.wb say for MU = 3 (wave-uniform): the t wave loads no link and skips the two SU(3) products and the row-2
+// rebuild everywhere else.  The boundary sign stays with pipe_sign.
+template <int MU, bool DAG, bool R12, bool NTB, bool DOT = false, bool DELTA = false, bool DW5 = false, bool FOLD = false, bool CINV = false, bool TG = false>
 __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int lane, real al_upd, real& nrm, real& dre, real& dim, int vb, real& dre2, real& dim2) {
     // DW5: this workgroup's slice s5 of the five-dimensional fields; block ids keep their XCD (b & 7) and the L5 slices of a chunk follow each other on it, so the
     // links of the chunk are fetched from the fabric once and hit the XCD's L2 for the other slices
@@ -863,7 +866,8 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
         cd sF[NS], uF[9], dF[2];
         if constexpr (FOLD && MU >= 1) fold_load_spinor<MU, NS, FF>(sF, boff(s.p ? a.in[0] : a.in[1], s.nf), a.gh_f[MU] + gslot, a.Fh[MU], gF);
         else load_comps12<FF, NS, false>(sF, boff(s.p ? a.in[0] : a.in[1], s.nf));
-        load_link_any<R12, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64);
+        if constexpr (TG && MU == 3) { if (s.wf) load_link_any<R12, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64); }      // (scalar branch)
+        else load_link_any<R12, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64);
         if constexpr (DELTA) { dF[0] = ld(boff(a.gauge + (s.p ? gpar : 0), s.uf) + 6 * 64); dF[1] = ld(boff(a.gauge + (s.p ? gpar : 0), s.uf) + 7 * 64); }
 #if LQCD_SDIR_GLDS
         // The backward neighbour's spinor goes global -> LDS with the asynchronous copy of gfx950 (global_load_lds_dwordx4: wave-uniform LDS base +
@@ -878,14 +882,25 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
                                                  (__attribute__((address_space(3))) void*)(&part[MU][j][0]), 16, 0, 0);
         }
 #endif
-        finish_link<R12>(uF);
+        if constexpr (!(TG && MU == 3)) finish_link<R12>(uF);
 #ifndef LQCD_F32
         if constexpr (DELTA) add_delta_row2(uF, dF);
 #endif
         project_regs<MU, SF>(h0, h1, sF);
         pipe_sign(h0, h1, sgF);
-        su3_mv<false>(chi0, uF, h0);
-        su3_mv<false>(chi1, uF, h1);
+        if constexpr (TG && MU == 3) {
+            if (s.wf) {
+                finish_link<R12>(uF);
+                su3_mv<false>(chi0, uF, h0);
+                su3_mv<false>(chi1, uF, h1);
+            } else {
+#pragma unroll
+                for (int c = 0; c < 3; c++) { chi0[c] = h0[c]; chi1[c] = h1[c]; }
+            }
+        } else {
+            su3_mv<false>(chi0, uF, h0);
+            su3_mv<false>(chi1, uF, h1);
+        }
         reconstruct<MU, SF>(acc, chi0, chi1);
     }
     __builtin_amdgcn_sched_barrier(0);      // the backward operands take the registers of the forward ones (3 waves per SIMD)
@@ -907,7 +922,8 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
             fold_unit_link<MU, R12>(uB, gB);
         } else {
             load_comps12<FB, NS, false>(sB, boff(s.p ? a.in[0] : a.in[1], s.nb));
-            load_link_any<R12, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
+            if constexpr (TG && MU == 3) { if (s.wb) load_link_any<R12, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64); }
+            else load_link_any<R12, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
         }
 #endif
         if constexpr (DELTA) {
@@ -915,14 +931,25 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
             dB[0] = NTB ? ld_nt(db + 6 * 64) : ld(db + 6 * 64);
             dB[1] = NTB ? ld_nt(db + 7 * 64) : ld(db + 7 * 64);
         }
-        finish_link<R12>(uB);
+        if constexpr (!(TG && MU == 3)) finish_link<R12>(uB);
 #ifndef LQCD_F32
         if constexpr (DELTA) add_delta_row2(uB, dB);
 #endif
         project_regs<MU, -SF>(h0, h1, sB);
         pipe_sign(h0, h1, sgB);
-        su3_mv<true>(chi0, uB, h0);
-        su3_mv<true>(chi1, uB, h1);
+        if constexpr (TG && MU == 3) {
+            if (s.wb) {
+                finish_link<R12>(uB);
+                su3_mv<true>(chi0, uB, h0);
+                su3_mv<true>(chi1, uB, h1);
+            } else {
+#pragma unroll
+                for (int c = 0; c < 3; c++) { chi0[c] = h0[c]; chi1[c] = h1[c]; }
+            }
+        } else {
+            su3_mv<true>(chi0, uB, h0);
+            su3_mv<true>(chi1, uB, h1);
+        }
         reconstruct<MU, -SF>(acc, chi0, chi1);
     }
 #endif
@@ -1029,10 +1056,9 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
     }
 }
 
-template <bool DAG, bool R12, bool NTB, bool DOT = false, bool DELTA = false, bool DW5 = false, bool FOLD = false, bool CINV = false>
-__global__ LQCD_DS_BOUNDS_S void wilson_dirsplit_s(PipeArgs a) {
-    __shared__ real2 part[4][12][64];  // 48 KiB (fp32: 24)
-    __shared__ double red[DOT ? 20 : 4];
+// the workgroup of the scalar-addressing kernel; its two entry points (wilson_dirsplit_s and the temporal-gauge wilson_dirsplit_s_tg) own the LDS
+template <bool DAG, bool R12, bool NTB, bool DOT, bool DELTA, bool DW5, bool FOLD, bool CINV, bool TG>
+__device__ __forceinline__ void dirsplit_s_block(const PipeArgs& a, real2 (*part)[12][64], double* red) {
     if ((a.upd_scal && a.upd_scal[S_DONE] != 0.0) || (a.skip && a.skip[S_DONE] != 0.0)) {
         if (a.scal_w && blockIdx.x == 0 && threadIdx.x == 0) a.scal_w[S_XDONE] = 1.0;
         return;
@@ -1063,10 +1089,10 @@ __global__ LQCD_DS_BOUNDS_S void wilson_dirsplit_s(PipeArgs a) {
     const int lane = threadIdx.x & 63;
     real nrm = 0.0, dre = 0.0, dim = 0.0, dre2 = 0.0, dim2 = 0.0;
     switch (w) {
-    case 0: sdir_wave<0, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2); break;
-    case 1: sdir_wave<1, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2); break;
-    case 2: sdir_wave<2, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2); break;
-    default: sdir_wave<3, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2); break;
+    case 0: sdir_wave<0, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2); break;
+    case 1: sdir_wave<1, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2); break;
+    case 2: sdir_wave<2, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2); break;
+    default: sdir_wave<3, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2); break;
     }
     if constexpr (DOT) {                // three sums per workgroup, the order of wilson_dirsplit's dot epilogue; five with a second inner product (dot_z2)
         const bool five = a.dotz2[0] != nullptr || a.dotz2[1] != nullptr;
@@ -1091,6 +1117,21 @@ __global__ LQCD_DS_BOUNDS_S void wilson_dirsplit_s(PipeArgs a) {
         if (threadIdx.x == 0) a.norm_partial[vb] = (red[0] + red[1]) + (red[2] + red[3]);
     }
 }
+template <bool DAG, bool R12, bool NTB, bool DOT = false, bool DELTA = false, bool DW5 = false, bool FOLD = false, bool CINV = false>
+__global__ LQCD_DS_BOUNDS_S void wilson_dirsplit_s(PipeArgs a) {
+    __shared__ real2 part[4][12][64];  // 48 KiB (fp32: 24)
+    __shared__ double red[DOT ? 20 : 4];
+    dirsplit_s_block<DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, false>(a, part, red);
+}
+#ifndef LQCD_F32
+// the plain 12-real instance on the temporal-gauge copy of the links (sdir_wave, TG): the norm and update-mode epilogues of the CG (fp64 build only)
+template <bool DAG, bool NTB>
+__global__ __launch_bounds__(256, 3) void wilson_dirsplit_s_tg(PipeArgs a) {
+    __shared__ real2 part[4][12][64];
+    __shared__ double red[4];
+    dirsplit_s_block<DAG, true, NTB, false, false, false, false, false, true>(a, part, red);
+}
+#endif
 
 // ------------------------------------------------------------------------------------------ staggered
 template <bool R12 = false>
@@ -1643,7 +1684,7 @@ static KArgs make_kargs(lqcd_ctx_s* c, const StencilCall& s, int TB) {
     KArgs k;
     k.g = c->geom;
     k.gauge = (const real2*)s.gauge;
-    k.gauge12 = (const real2*)s.gauge12;   // elements of this build's precision (the caller matches prec)
+    k.gauge12 = (const real2*)(s.gauge12t ? s.gauge12t : s.gauge12);   // elements of this build's precision (the caller matches prec); the temporal-gauge copy has the layout of the 12-real one
     k.clover = (const real2*)s.clover;     // elements of this build's precision (the caller matches prec)
     for (int p = 0; p < 2; p++) { k.out[p] = (real2*)s.out[p]; k.in[p] = (const real2*)s.in[p]; k.xin[p] = (const real2*)s.xin[p]; }
     k.a = s.a; k.b = s.b; k.r = s.r;
@@ -1843,6 +1884,10 @@ static int launch_dirsplit_fold(lqcd_ctx_s* c, const StencilCall& s, const KArgs
 
 int launch_stencil_interior(lqcd_ctx_s* c, const StencilCall& s) {
     if (s.dw_ls > 1 && !stencil_dw5_applies(c, s)) { set_error("stencil: the five-dimensional launch does not apply to this call (domainwall.hip checks before asking)"); return LQCD_ERR_UNSUPPORTED; }
+    if (s.gauge12t && (kF32Build || s.kind != LQCD_WILSON || s.r != 1.0 || c->tun.dslash_variant != 1)) {      // (the tunables moved under an open CG session)
+        set_error("stencil: temporal-gauge links are read by the 12-real Wilson r = 1 direction-split kernels only");
+        return LQCD_ERR_UNSUPPORTED;
+    }
     if (use_dirsplit(c, s.kind, s.r)) {
         KArgs k = make_kargs(c, s, 64);
         const size_t pad = (size_t)c->tun.lds_pad_kb * 1024;
@@ -1970,8 +2015,15 @@ int launch_stencil_interior(lqcd_ctx_s* c, const StencilCall& s) {
                                           else hipLaunchKernelGGL((wilson_dirsplit_pipe<D, R, false>), pg, pb, 0, c->stream, a); } \
                            else { if (ntb) hipLaunchKernelGGL((wilson_dirsplit_s<D, R, true>), pg, pb, 0, c->stream, a); \
                                   else hipLaunchKernelGGL((wilson_dirsplit_s<D, R, false>), pg, pb, 0, c->stream, a); } } while (0)
+#ifndef LQCD_F32
+#define LQ_TG(D) do { if (ntb) hipLaunchKernelGGL((wilson_dirsplit_s_tg<D, true>), pg, pb, 0, c->stream, a); \
+                      else hipLaunchKernelGGL((wilson_dirsplit_s_tg<D, false>), pg, pb, 0, c->stream, a); } while (0)
+            if (s.gauge12t && !persist && k.g.L[3] >= 2) { if (s.dagger) LQ_TG(true); else LQ_TG(false); }      // temporal-gauge links: the t wave skips the unit links
+            else
+#endif
             if (k.gauge12) { if (s.dagger) LQ_PIPE(true, true); else LQ_PIPE(false, true); }
             else { if (s.dagger) LQ_PIPE(true, false); else LQ_PIPE(false, false); }
+#undef LQ_TG
 #undef LQ_PIPE
             }
 #if !defined(LQCD_F32) && defined(LQCD_VARIANTS)   // opt-in variants 2-8 (stencil_alt.hip, -DLQCD_VARIANTS builds): fp64 only -- the fp32 build (paired-component fields) has the direction-split and the
@@ -2137,6 +2189,12 @@ bool wilson_pipe_applies(lqcd_ctx_s* c, int kind, double r, int parity_mode, boo
     const int nvirt = ((g.Vh + 63) / 64) * (parity_mode == 2 ? 2 : 1);
     if (c->tun.dslash_pipe == 2 || c->tun.dslash_pipe == 3) return true;      // hardware dispatch order: no minimum size
     return nvirt >= std::max(1, c->tun.pipe_min_chunks) * wilson_pipe_grid(c, nvirt, 0);
+}
+// A full-lattice fp64 application that is handed the temporal-gauge links (StencilCall::gauge12t) runs the TG instances of the scalar-addressing kernel: asked by the
+// CG before it rotates anything.  (Launches that do not -- the small-lattice alpha_partials form -- read the unit links of the copy and compute the same bits.)
+bool stencil_tgauge_applies(lqcd_ctx_s* c, int kind, double r, bool clover) {
+    if (any_partitioned(c) || c->tun.dslash_pipe != 2 || c->tun.gauge_recon != 12 || c->geom.L[3] < 2) return false;
+    return wilson_pipe_applies(c, kind, r, 2, clover);
 }
 // The folded one-stream halo schedule (apply.hip stencil_apply; tunable halo_fold): pack -> exchange -> ONE stencil launch that reads the ghost buffers itself.
 // Where: the RCCL path with schedule 3 chosen; Wilson (r = 1 calls: plain, clover epilogue, inverse clover blocks on the hop sum) and staggered, fp64 and the fp32
