@@ -77,8 +77,8 @@ int lqcd_ctx_sync(lqcd_ctx_t ctx);
  * [default], 2 hop split, 3 persistent hop split, 4 lane split = four directions in the four 16-lane rows of a wave combined by
  * v_permlane swaps, 5 direction split with the footprint of four workgroups per CU, 6 direction split with the x / y neighbour spinors staged
  * through LDS, 7 both parities of a chunk in one 512-thread workgroup; variants 2-8 exist only in LQCD_VARIANTS=1 builds of the library --
- * read-only key variants_built -- and run variant 1 otherwise), dslash_block, xcd_remap, xcd_nsub, xcd_ysplit, cg_fused (0 reference form, 1, 2 fused
- * [default]), graph (1: hipGraph replay of CG bursts), gauge_recon (12 [default]: the split kernels read two rows per link and rebuild the
+ * read-only key variants_built -- and run variant 1 otherwise), dslash_block, xcd_remap, xcd_nsub, xcd_ysplit, cg_fused (0 reference form, 1, 2 fused,
+ * 3 [default]: 2 with the residual ring, see cg_rring), graph (1: hipGraph replay of CG bursts), gauge_recon (12 [default]: the split kernels read two rows per link and rebuild the
  * third -- applied only while every link of the field is unitary to 1e-14, results within the fp64 Dslash tolerance; 18: all
  * 18 stored reals are always read), recon_active (read-only: did the last Wilson application use the 12-real links), nt_gauge (bit 0 [default]: the backward = last use of a link is a non-temporal load; bit 1: the forward use too), nt_store (1 [default]:
  * non-temporal output stores), lds_pad_kb, persist_per_cu, dslash_pipe (forms of the Wilson r = 1 direction-split kernel on lattices whose z-planes are whole chunks;
@@ -98,7 +98,12 @@ int lqcd_ctx_sync(lqcd_ctx_t ctx);
  * cg_skip_done, cg_defer_x (2: the fused CG updates x every second iteration with both search directions, p alternating between
  * two buffers -- 9 instead of 10 spinor passes per iteration on average, identical iterates; K = 3..8 (round 5): a ring of K search-direction buffers,
  * x += K terms every K-th iteration, (4 K + 1) / K update passes per iteration; 1 [default]: 2 on an unpartitioned lattice, 8 on a partitioned one (what was measured
- * faster in each case); 0: x every iteration),
+ * faster in each case); 0: x every iteration; under cg_fused = 3 it has no meaning where the residual ring applies),
+ * cg_rring (cg_fused = 3; K = 4 [default], 2 or 8, 0: off, other values are refused: the fp64 Wilson D^+D CG -- r = 1, no clover term, one unpartitioned GPU without a
+ * communicator, scalar-addressing kernel, beyond cg_small -- forms D p by the recurrence D p' = D r' + beta D p from the residual D^+ has just written, keeps the K
+ * residuals of a batch in a ring and brings p and x up to date once per K iterations in one streaming launch; the recurrence restarts from an exact D p there.  2064 instead of
+ * 2400 bytes per site and iteration at K = 4, K - 2 more work vectors; the iterates equal those of cg_fused = 2 to rounding; everything else runs as cg_fused = 2.
+ * Read-only cg_rring_active: the K in use by the last CG set-up, 0 if the form did not apply),
  * halo_fold (1 [default], round 5: where the collective timing picks the one-stream halo schedule 3, the stencil launch takes the boundary hops from the ghost
  * buffers itself -- no exterior kernel, for every operator and both precisions; read-only halo_fold_active), cg_persist (1 [default]: a staggered CG on an unpartitioned lattice of
  * at most 256 chunks of 64 sites runs as ONE launch -- initial residual and all iterations, two grid-wide synchronisations per iteration, every wait bounded: if the workgroups are not all resident (a busy GPU) x is left untouched, the solve is
@@ -449,6 +454,12 @@ int lqcd_bench_dslash(lqcd_op_t op, lqcd_spinor_t out, lqcd_spinor_t in, int dag
                       double* ms_per_apply);
 /* ms per CG iteration over a fixed window of niter iterations (after `warm` untimed iterations) */
 int lqcd_bench_cg(lqcd_op_t op, lqcd_spinor_t x, lqcd_spinor_t b, int warm, int niter, double* ms_per_iter);
+
+/* one full-lattice stencil launch with the epilogues of the fused CG, on the caller's fields (tests): mode 0 dst = D in; 1 (update mode) dst = src - coef D in,
+ * src may be dst; 2 (recurrence mode, scalar-addressing Wilson kernel) dst = D in + coef dst.  dagger: D^+; tgauge: on the temporal-gauge copy of the links;
+ * done != 0: the solver's done flag is raised for the launch (modes 1 and 2 then leave dst untouched).  norm2 = the sum of the |.|^2 partials of the launch */
+int lqcd_bench_stencil_epilogue(lqcd_op_t op, lqcd_spinor_t dst, lqcd_spinor_t src, lqcd_spinor_t in, int dagger, int mode, int tgauge, double coef, int done,
+                                double* norm2);
 
 /* CG session for externally timed windows (bench.py brackets these with its own barriers/clock):
  * begin = r = b - D^+D x, p = r; iterate = enqueue n iterations (exit test disabled) and wait; end = release scratch */

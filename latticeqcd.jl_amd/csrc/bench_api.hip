@@ -172,6 +172,44 @@ extern "C" int lqcd_bench_cg(lqcd_op_t op, lqcd_spinor_t x, lqcd_spinor_t b, int
     return st;
 }
 
+// one launch of a full-lattice stencil with the epilogues the fused CG uses, on caller-owned fields (tests): mode 0 plain, dst = D in; 1 update mode, dst = src - coef D in
+// (src may be dst: the in-place launch); 2 recurrence mode, dst = D in + coef dst.  D^+ with dagger, the temporal-gauge copy of the links with tgauge, `done` is written to
+// the done flag first (modes 1 and 2 are then no-ops) and cleared afterwards.  norm2: the sum of the launch's |.|^2 partials.
+extern "C" int lqcd_bench_stencil_epilogue(lqcd_op_t op, lqcd_spinor_t dst, lqcd_spinor_t src, lqcd_spinor_t in, int dagger, int mode, int tgauge, double coef, int done, double* norm2) {
+    LQCHK(check_full(op, dst, in, "lqcd_bench_stencil_epilogue"));
+    ARGCHK(mode >= 0 && mode <= 2 && norm2 && (mode != 1 || src), "lqcd_bench_stencil_epilogue: bad arguments");
+    if (mode == 1) LQCHK(check_full(op, src, in, "lqcd_bench_stencil_epilogue"));
+    ARGCHK(in != dst && in != src, "lqcd_bench_stencil_epilogue: the hop operand must not be written");
+    lqcd_ctx_s* c = op->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    const double2* gt = nullptr;
+    if (tgauge) {
+        ARGCHK(gauge_ensure_tgauge(op->gauge) == LQCD_OK && op->gauge->tgauge_ok, "lqcd_bench_stencil_epilogue: no temporal-gauge copy of these links");
+        gt = op->gauge->data12t;
+    }
+    double sc[3] = {coef, coef, done ? 1.0 : 0.0};      // S_ALPHA, S_BETA, S_DONE
+    static_assert(S_BETA == S_ALPHA + 1 && S_DONE == S_ALPHA + 2, "lqcd_bench_stencil_epilogue: scalar slots");
+    HIPCHK(hipMemcpyAsync(c->d_scal + S_ALPHA, sc, sizeof(sc), hipMemcpyHostToDevice, c->stream));
+    apply_bc(c, op->bc);
+    StencilCall s;
+    LQCHK(make_full_call(op, dst, in, dagger, s));
+    s.gauge12t = gt;
+    s.norm_partial = c->d_partial;
+    if (mode) {
+        s.upd_scal = c->d_scal;
+        for (int q = 0; q < 2; q++) { s.upd[q] = spinor_block(dst, q); if (mode == 1 && src != dst) s.upd_src[q] = spinor_block(src, q); }
+        s.upd_rec = mode == 2 ? 1 : 0;
+    }
+    int st = stencil_apply(c, s);
+    if (st == LQCD_OK) st = reduce_to_slot(c, stencil_num_partials(c, op->kind, op->r, 2, 0, op_fused_clover(op)), 1, S_PQ, true);
+    sc[2] = 0.0;
+    HIPCHK(hipMemcpyAsync(c->d_scal + S_ALPHA, sc, sizeof(sc), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_scal, c->d_scal + S_PQ, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *norm2 = c->h_scal[0];
+    return st;
+}
+
 // CG session (externally timed windows); the state lives in the context, one open session per context
 namespace lqcd {
 struct CgSession { lqcd_op_s* op = nullptr; lqcd_spinor_s* x = nullptr; CgWork w; };

@@ -345,6 +345,8 @@ static int* param_ptr(lqcd_ctx_s* c, const char* key) {
     if (!strcmp(key, "halo_fold")) return &c->tun.halo_fold;
     if (!strcmp(key, "halo_fold_active")) return &c->tun.halo_fold_active;
     if (!strcmp(key, "cg_defer_x")) return &c->tun.cg_defer_x;
+    if (!strcmp(key, "cg_rring")) return &c->tun.cg_rring;
+    if (!strcmp(key, "cg_rring_active")) return &c->tun.cg_rring_active;
     if (!strcmp(key, "staggered_parity_solve")) return &c->tun.staggered_parity_solve;
     if (!strcmp(key, "halo_tuned_us0")) return &c->tun.halo_tuned_us[0];
     if (!strcmp(key, "halo_tuned_us1")) return &c->tun.halo_tuned_us[1];
@@ -393,6 +395,7 @@ extern "C" int lqcd_ctx_set_param(lqcd_ctx_t c, const char* key, int value) {
     ARGCHK(p, std::string("lqcd_ctx_set_param: unknown key ") + key);
     if (!strcmp(key, "dslash_block")) ARGCHK(value == 64 || value == 128 || value == 256, "dslash_block must be 64, 128 or 256");
     if (!strcmp(key, "halo_stream_mode")) ARGCHK(value >= -1 && value <= 4, "halo_stream_mode must be -1 (timed once) or 0..4");
+    if (!strcmp(key, "cg_rring")) ARGCHK(value == 0 || value == 2 || value == 4 || value == 8, "cg_rring must be 0 (off), 2, 4 or 8 (it divides the 8 iterations of a captured burst)");
     if (!strcmp(key, "halo_inject_us")) ARGCHK(value >= 0 && value <= 100000, "halo_inject_us: 0..100000");
     if ((!strcmp(key, "lazy_links") || !strcmp(key, "lazy_merge")) && !value) LQCHK(links_flush_of(c));      // switching to eager calls: what is recorded runs now
     *p = value;

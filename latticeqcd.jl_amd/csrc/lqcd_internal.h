@@ -324,7 +324,9 @@ __device__ inline double shfl_tree_sum(double s) {      // lane 0 holds the sum 
 // ---------------------------------------------------------------- the CG / BiCGStab scalar steps behind a reduction (one thread)
 // slots of the device scalar block d_scal used by the solvers
 enum { S_RED0 = 0, S_RR = 8, S_PQ = 9, S_ALPHA = 10, S_BETA = 11, S_DONE = 12, S_ITERS = 13, S_EPS = 14, S_RRNEW = 15, S_XDONE = 16, S_RROLD = 17, S_APREV = 18,
-       S_AHIST = 64 };      // S_AHIST .. +7: the step lengths of the search directions whose x update is still pending (cg_defer_x >= 3: ring of p buffers)
+       S_BSTART = 19,       // cg_fused = 3: the value of S_ITERS at the start of the batch whose x / p update is pending (S_ITERS - S_BSTART iterations are)
+       S_AHIST = 64,        // S_AHIST .. +7: the step lengths of the search directions whose x update is still pending (cg_defer_x >= 3: ring of p buffers; cg_fused = 3: the batch)
+       S_BHIST = 72 };      // S_BHIST .. +7: cg_fused = 3, the beta of the pending iterations (the host never reads either history)
 // BiCGStab block (complex scalars are two consecutive doubles; B_TS..B_TT and B_RR..B_RHO1 are filled by one 3-value reduction)
 enum { B_RHO = 24, B_R0V = 26, B_VV = 28, B_ALPHA = 29, B_SS = 31, B_TS = 32, B_TT = 34, B_OMEGA = 35, B_RR = 37, B_RHO1 = 38, B_BETA = 40,
        B_DONE = 42, B_ITERS = 43, B_EPS = 44, B_HALF = 45, B_RES = 46, B_RHOB = 47, B_TS5 = 49, B_UNSURE = 54, B_END = 55 };   // B_TS5: <t, s>, |t|^2, <r0, t> of the merged chain (bicg_fused = 4), one 5-value reduction;      // B_R0V..B_VV, B_TS..B_TT and B_RR..B_RHO1 are filled by one
@@ -337,6 +339,22 @@ __device__ inline void cg_scalar_step(double* s, int op) {
         if (s[S_DONE] != 0.0) return;
         const double rrn = s[S_RRNEW];
         s[S_BETA] = rrn / s[S_RR];
+        s[S_RR] = rrn;
+        s[S_ITERS] += 1.0;
+        if (rrn < s[S_EPS]) s[S_DONE] = 1.0;
+    } else if (op == 7 || op == 9) {
+        // cg_fused = 3 (solvers.hip, residual ring): op 1 + alpha into the history of the pending batch; 9 opens a batch (the launch behind cg_batch_px)
+        if (s[S_DONE] != 0.0) { s[S_XDONE] = 1.0; return; }
+        if (op == 9) s[S_BSTART] = s[S_ITERS];
+        const double al = s[S_RR] / s[S_PQ];
+        s[S_ALPHA] = al;
+        s[S_AHIST + ((int)(s[S_ITERS] - s[S_BSTART]) & 7)] = al;
+    } else if (op == 8) {      // op 2 + beta into the history
+        if (s[S_DONE] != 0.0) return;
+        const double rrn = s[S_RRNEW];
+        const double be = rrn / s[S_RR];
+        s[S_BETA] = be;
+        s[S_BHIST + ((int)(s[S_ITERS] - s[S_BSTART]) & 7)] = be;
         s[S_RR] = rrn;
         s[S_ITERS] += 1.0;
         if (rrn < s[S_EPS]) s[S_DONE] = 1.0;
@@ -453,7 +471,10 @@ struct Tunables {
                               // too.  Measured at 32^3x64 (profiles/r02_nt_sweep.log): bit 0 -1.5..2.5 %, bit 1 +40 % (the second use then misses
                               // the Infinity Cache as well)
     int nt_store = 1;         // output spinor stored non-temporally (it is not read again by this kernel: keeps its lines out of the L2) -1..3 %
-    int cg_fused = 2;         // 0: reference form (c1 = p.q), 1: |Dp|^2 from the stencil, 2: + r-update fused into D^+, x/p updates merged
+    int cg_fused = 3;         // 0: reference form (c1 = p.q), 1: |Dp|^2 from the stencil, 2: + r-update fused into D^+, x/p updates merged, 3 (default): 2 +, where
+                              // the scalar-addressing Wilson kernel runs on one unpartitioned GPU, D p by recurrence from D r and p, x updated once per cg_rring iterations
+    int cg_rring = 4;         // cg_fused = 3: K = 2, 4 or 8 residual slots (p and x are brought up to date every K-th iteration; K divides the 8 iterations of a captured burst); 0: form off
+    int cg_rring_active = 0;  // read-only: the K in use by the last CG set up through cg_setup, 0 if the form did not apply
     int graph = 0;            // capture solver iterations in a hipGraph
     int persist_per_cu = 2;   // variant 3: resident workgroups per CU
     int dslash_pipe = 2;      // Wilson r = 1, variant 1, lattices whose z-planes are whole chunks: 1 = the persistent, software-pipelined form of the
@@ -982,6 +1003,11 @@ struct StencilCall {
     // scalar block (upd_scal[S_ALPHA]); the kernel is a no-op once upd_scal[S_DONE] is set.  q = D^+ D p is never written.
     const double* upd_scal = nullptr;
     double2* upd[2] = {nullptr, nullptr};
+    // scalar-addressing Wilson kernel only (launch_stencil_interior refuses everything else).  upd_src: the centre read of update mode comes from here and the store goes
+    // to upd (r_k from one slot of a ring, r_{k+1} into the next); null: from upd, in place.  upd_rec = 1, recurrence mode: upd holds s_old and receives
+    // s = v + beta s_old in place, beta = upd_scal[S_BETA]; |s|^2 partials; the plain launch's store policy; a no-op once upd_scal[S_DONE] is set.
+    const double2* upd_src[2] = {nullptr, nullptr};
+    int upd_rec = 0;
     const double* skip_flag = nullptr;  // device scalar block: the interior launch is a no-op once skip_flag[S_DONE] is set (iterations
                                         // enqueued behind the converging one in a burst)
     // small lattices (cg_small): no separate reduction launches.  The update-mode kernel sums the <= 1024 block partials of the previous
@@ -1112,6 +1138,7 @@ int gauge_ensure_recon12(lqcd_gauge_s* g);   // (re)builds the 12-real copy if t
 int gauge_ensure_recon12d(lqcd_gauge_s* g);  // (re)builds the "12 + delta" copy; sets g->delta_ok
 int gauge_ensure_tgauge(lqcd_gauge_s* g);    // (re)builds G and the temporal-gauge copy of the 12-real links if the field changed; sets g->tgauge_ok
 int spinor_gauge_rotate(lqcd_ctx_s* c, const double2* gfix, double2* dst, const double2* src, int adjoint);   // solvers.hip: dst = G src / G^+ src on a full Wilson field (dst may be src)
+bool stencil_sdir_applies(lqcd_ctx_s* c, int kind, double r, bool clover);     // stencil.hip: a full-lattice fp64 application takes the scalar-addressing Wilson kernel (upd_src / upd_rec exist there)
 bool stencil_tgauge_applies(lqcd_ctx_s* c, int kind, double r, bool clover);   // stencil.hip: a full-lattice fp64 application with 12-real links would take the TG instances
 int plaquette_local_sum(lqcd_gauge_s* g, const double2* const ghost[4], double* sum);
 int gauge_pack_face(lqcd_gauge_s* g, int mu, double2* dst);

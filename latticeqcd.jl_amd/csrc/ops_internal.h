@@ -23,11 +23,15 @@ struct CgWork {
     lqcd_spinor_s *r, *p, *q, *tmp;
     uint64_t pack_epoch = 0; // value of the context's halo_epoch right after that pack
     bool p_packed = false;   // partitioned lattice, halo_fuse bit 1: the send buffers hold the faces of the current search direction (packed by the last x/p update)
-    int form = -1;      // iteration form fixed at cg_setup (0 plain, 1 deferred x, 2 small-lattice): the tunables may change while a session is open
+    int form = -1;      // iteration form fixed at cg_setup (0 plain, 1 deferred x, 2 small-lattice, 3 residual ring): the tunables may change while a session is open
     int k = 0;          // iterations enqueued so far (parity selects the p buffer when the x update is deferred: p_k lives in p for even k, in q for odd k)
     int ring = 2;       // form 1: search-direction buffers in rotation (2: p, q; K > 2: p, q, more[0..K-3]; p_k lives in buffer k % K), fixed at cg_setup
     lqcd_spinor_s* more[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     lqcd_spinor_s* buf(int j) const { return j == 0 ? p : j == 1 ? q : more[j - 2]; }
+    // form 3 (cg_fused = 3, solvers.hip "residual ring"): r_k lives in slot k % rring (slots: r, q, more[0..rring-3]), p in p, s = D p in tmp
+    int rring = 0;
+    bool flushed = false;    // form 3: the pending x terms have been applied (cg_flush_x); the window is over
+    lqcd_spinor_s* slot(int j) const { return j == 0 ? r : j == 1 ? q : more[j - 2]; }
     // temporal gauge (decided once in cg_setup): x, r and the search directions are G times the caller's vectors and every stencil call of the iteration reads
     // the rotated links; cg_finish rotates x back
     bool tgauge = false;

@@ -289,6 +289,45 @@ __global__ __launch_bounds__(UB) void cg_flush_ring(const double* __restrict__ s
         x[i] = xv;
     }
 }
+// ---- cg_fused = 3, the residual ring: D p by recurrence from D r; p and x brought up to date once per K iterations (tunable cg_rring = K = 2, 4, 8).
+// With s_k = D p_k and p_{k+1} = r_{k+1} + beta_k p_k:  s_{k+1} = D r_{k+1} + beta_k s_k.  The stencil is applied to the residual the D^+ before it has just written
+// (recurrence mode of the scalar-addressing kernel: s read at the centre, s = v + beta s stored in place), so p is needed only to accumulate x: the K residuals of a
+// batch stay in a ring of K slots (update-mode D^+ reads r_k from slot k % K and writes r_{k+1} to the next), alpha_k / beta_k go to S_AHIST / S_BHIST, and every K-th
+// iteration ONE streaming launch (cg_batch_px) forms x and p by the fma sequence of cg_update_xp; the D behind it is a plain D on the fresh p, which restarts the
+// recurrence (its rounding error lives for at most K - 1 steps).  Per site and iteration: 864 B (D, recurrence mode) + 864 B (D^+) + ((K + 4) 192 + 672 - 864) / K B
+// = 2208 / 2064 / 1992 B for K = 2 / 4 / 8, against the 2400 B of the two-buffer deferred-x form; 4 + 1 / K launches instead of 5.
+// Where: cg_setup's gate (cg_rring_wanted) -- Wilson, r = 1, no clover term, one unpartitioned GPU without a communicator, the scalar-addressing kernel, beyond cg_small.
+// Costed and not built: (a) the batch folded into the D behind it -- the stencil would read the K residuals and p at every NEIGHBOUR as well (the new p is its
+// hop operand): 8 x (K + 1) more reads than the K + 4 streams it saves; (b) K that does not divide 8 -- a captured burst of 8 iterations bakes the slot roles in, the
+// replay must find the ring where it left it; (c) staggered, fp32 / mixed-precision, multi-shift, even-odd and partitioned solvers: the same recurrence applies, their
+// kernels have no centre read separate from the store ("not done").
+struct CgSlots { const double2* r[8]; };      // slot of r_{b+j+1}, j = 0..7, b the first iteration of the batch (entries >= K unused); indexed by unrolled constants only
+// x += alpha_j p_j, p_{j+1} = r_{j+1} + beta_j p_j for the pending iterations j = 0 .. np - 1, oldest first (np = S_ITERS - S_BSTART, from the device).  fin = 0 (batch
+// boundary inside a window): np = K, writes x and p; a no-op once the solve is done.  fin = 1 (cg_flush_x: a converged solve, an exhausted one, the end of a window):
+// applies the np pending terms to x, whatever the done flag says, and forms no p nobody uses.
+template <bool NT>
+__global__ __launch_bounds__(UB) void cg_batch_px(const double* __restrict__ s, double2* __restrict__ x, double2* __restrict__ p, CgSlots sl, int fin, size_t n) {
+    const int np = (int)(s[S_ITERS] - s[S_BSTART]);
+    if (np <= 0 || np > 8 || (!fin && s[S_DONE] != 0.0)) return;
+    double al[8], be[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) { al[j] = j < np ? s[S_AHIST + j] : 0.0; be[j] = j < np ? s[S_BHIST + j] : 0.0; }
+    for (size_t i = (size_t)blockIdx.x * UB + threadIdx.x; i < n; i += (size_t)gridDim.x * UB) {
+        double2 xv = ldx<NT>(x + i), pv = ldx<NT>(p + i);
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            if (j < np) {
+                xv.x = fma(al[j], pv.x, xv.x); xv.y = fma(al[j], pv.y, xv.y);
+                if (!fin || j < np - 1) {
+                    const double2 rv = ldx<NT>(sl.r[j] + i);
+                    pv.x = fma(be[j], pv.x, rv.x); pv.y = fma(be[j], pv.y, rv.y);
+                }
+            }
+        }
+        stx<NT>(x + i, xv);
+        if (!fin) stx<NT>(p + i, pv);
+    }
+}
 // p = r + beta p
 __global__ __launch_bounds__(UB) void cg_update_p(const double* __restrict__ s, double2* __restrict__ p, const double2* __restrict__ r, size_t n) {
     if (s[S_DONE] != 0.0) return;
@@ -415,8 +454,22 @@ static CgRing cg_ring_pending(const CgWork& w, int m) {      // the buffers of p
     for (int j = 0; j < 8; j++) ring.b[j] = j < m ? w.buf((w.k - m + j) % w.ring)->data : nullptr;
     return ring;
 }
+static int cg_batch_launch(lqcd_ctx_s* c, lqcd_spinor_s* x, CgWork& w, int fin) {
+    CgSlots sl;
+    for (int j = 0; j < 8; j++) sl.r[j] = j < w.rring ? w.slot((j + 1) % w.rring)->data : nullptr;
+    const dim3 g(stream_grid(c, x->elems)), b(UB);
+    if (c->tun.nt_blas) hipLaunchKernelGGL(cg_batch_px<true>, g, b, 0, c->stream, c->d_scal, x->data, w.p->data, sl, fin, x->elems);
+    else hipLaunchKernelGGL(cg_batch_px<false>, g, b, 0, c->stream, c->d_scal, x->data, w.p->data, sl, fin, x->elems);
+    HIPCHK(hipGetLastError());
+    return LQCD_OK;
+}
 int cg_flush_x(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
     lqcd_ctx_s* c = op->ctx;
+    if (w.form == 3) {      // residual ring: the pending terms of the open batch (also behind the converging iteration: no launch of the iteration updates x)
+        if (w.flushed || w.k == 0) return LQCD_OK;
+        w.flushed = true;      // (a window is never continued after its flush)
+        return cg_batch_launch(c, x, w, 1);
+    }
     const bool deferred = w.form >= 0 ? w.form == 1 : cg_defers_x(op);     // the form the iterations were enqueued in (recorded by cg_setup)
     if (deferred && w.ring > 2) {
         const int m = w.k % w.ring;       // directions p_{k-m} .. p_{k-1} are still to be added
@@ -456,9 +509,63 @@ static bool cg_tgauge_wanted(lqcd_op_s* op) {
     return gauge_ensure_tgauge(op->gauge) == LQCD_OK && op->gauge->tgauge_ok;
 }
 
+// one iteration of the residual-ring form (see cg_batch_px): k % K = 0: batch kernel (nothing pending at k = 0: a no-op that keeps a captured burst replayable), plain D on p;
+// otherwise D in recurrence mode on r_k.  Then alpha (+ history), D^+ from slot k % K into the next, beta (+ history, convergence).  No update launch.
+static int cg_enqueue_rring(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
+    lqcd_ctx_s* c = op->ctx;
+    if (w.flushed) { set_error("CG: the window was flushed; it cannot be continued"); return LQCD_ERR_ARG; }
+    const double2* gt = w.tgauge ? w.links_t : nullptr;
+    const int K = w.rring, m = w.k % K;
+    const int nbs = stencil_num_partials(c, op->kind, op->r, 2, 0, op_fused_clover(op));
+    lqcd_spinor_s *rk = w.slot(m), *rn = w.slot((m + 1) % K);
+    StencilCall s1;
+    if (m == 0) {
+        LQCHK(cg_batch_launch(c, x, w, 0));
+        apply_bc(c, op->bc);
+        LQCHK(make_full_call(op, w.tmp, w.p, 0, s1));
+        s1.skip_flag = c->tun.cg_skip_done ? c->d_scal : nullptr;
+    } else {
+        apply_bc(c, op->bc);
+        LQCHK(make_full_call(op, w.tmp, rk, 0, s1));
+        s1.upd_scal = c->d_scal;      // (its done flag is the mandatory one: the store is in place)
+        s1.upd[0] = spinor_block(w.tmp, 0);
+        s1.upd[1] = spinor_block(w.tmp, 1);
+        s1.upd_rec = 1;
+    }
+    s1.gauge12t = gt;
+    s1.norm_partial = c->d_partial;
+    LQCHK(stencil_apply(c, s1));
+    LQCHK(reduce_to_slot(c, nbs, 1, S_PQ, true, m == 0 ? 9 : 7));      // + alpha = rr / |s|^2 into the history (9: a batch opens)
+    apply_bc(c, op->bc);
+    StencilCall s2;
+    LQCHK(make_full_call(op, rn, w.tmp, 1, s2));
+    s2.gauge12t = gt;
+    s2.norm_partial = c->d_partial;
+    s2.upd_scal = c->d_scal;
+    for (int q = 0; q < 2; q++) { s2.upd[q] = spinor_block(rn, q); s2.upd_src[q] = spinor_block(rk, q); }
+    LQCHK(stencil_apply(c, s2));
+    LQCHK(reduce_to_slot(c, nbs, 1, S_RRNEW, true, 8));               // + beta into the history, convergence flag
+    w.k++;
+    return LQCD_OK;
+}
+// the residual ring applies: Wilson, r = 1, no clover term, one unpartitioned GPU without a communicator, every stencil launch of the iteration takes the
+// scalar-addressing kernel (12-real, 18-real, 12 + delta or temporal-gauge instance).  Returns K (tunable cg_rring), 0 if not.  Asked by cg_setup behind the cg_small test.
+static int cg_rring_wanted(lqcd_op_s* op, const CgWork& w) {
+    lqcd_ctx_s* c = op->ctx;
+    const int K = c->tun.cg_rring;
+    if (c->tun.cg_fused < 3 || !(K == 2 || K == 4 || K == 8)) return 0;
+    if (op->kind != LQCD_WILSON || op->r != 1.0 || op->csw != 0.0 || any_partitioned(c) || c->has_comm || !c->local_peers.empty()) return 0;
+    if (!stencil_sdir_applies(c, op->kind, op->r, op_fused_clover(op))) return 0;
+    StencilCall s;      // the links this operator's calls read: the 18 stored reals take the kernel only with dslash_s18
+    if (make_full_call(op, w.tmp, w.p, 0, s) != LQCD_OK) return 0;
+    if (!(w.tgauge || s.gauge12 || c->tun.dslash_s18)) return 0;
+    return K;
+}
+
 int cg_enqueue_iteration(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
     lqcd_ctx_s* c = op->ctx;
     const size_t n = x->elems;
+    if (w.form == 3) return cg_enqueue_rring(op, x, w);
     const double2* gt = w.tgauge ? w.links_t : nullptr;      // temporal gauge: every stencil call below reads the rotated links
     const int nbs_small = stencil_num_partials(c, op->kind, op->r, 2, 0, op_fused_clover(op));
     // the iteration form was fixed when the solve / session was set up (a tunable changed in between must not split a pending deferred update)
@@ -626,13 +733,26 @@ int cg_setup(lqcd_op_s* op, lqcd_spinor_s* x, lqcd_spinor_s* b, CgWork& w, doubl
     LQCHK(blas_axpy(c, -1.0, 0.0, w.q->data, w.r->data, n));
     HIPCHK(hipMemcpyAsync(w.p->data, w.r->data, n * sizeof(double2), hipMemcpyDeviceToDevice, c->stream));
     LQCHK(blas_norm2(c, w.r->data, n, rr0, true));
-    double init[9] = {*rr0, 0, 0, 0, 0, 0, eps, 0, 0};   // S_RR .. S_XDONE
+    double init[12] = {*rr0, 0, 0, 0, 0, 0, eps, 0, 0, 0, 0, 0};   // S_RR .. S_XDONE, S_RROLD, S_APREV, S_BSTART
+    static_assert(S_BSTART - S_RR == 11, "cg_setup: the scalar block it initialises ends at S_BSTART");
     HIPCHK(hipMemcpyAsync(c->d_scal + S_RR, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     w.k = 0; w.p_packed = false;
     w.form = (c->tun.cg_fused >= 2 && c->tun.cg_small && cg_small_ok(op, stencil_num_partials(c, op->kind, op->r, 2, 0, op_fused_clover(op)))) ? 2
              : (cg_defers_x(op) ? 1 : 0);
     w.ring = 2;
+    w.rring = 0; w.flushed = false;
+    if (w.form != 2) {      // cg_fused = 3, the residual ring (its K does not depend on `graph`: 2, 4, 8 divide a captured burst): K - 2 more vectors, or the forms above if the pool cannot grow
+        const int K = cg_rring_wanted(op, w);
+        bool ok = K > 0;
+        for (int j = 0; j < K - 2 && ok; j++) {
+            if (!w.more[j]) w.more[j] = scratch_get(c, x->kind, LQCD_FULL);
+            ok = w.more[j] != nullptr;
+        }
+        if (ok) { w.form = 3; w.rring = K; }
+        else for (lqcd_spinor_s*& f : w.more) { if (f) scratch_put(f); f = nullptr; }
+    }
+    c->tun.cg_rring_active = w.rring;
     if (w.form == 1) {      // the ring of search-direction buffers (cg_defer_x = K): K - 2 more vectors, or the two-buffer form if the pool cannot grow
         int want = cg_ring_wanted(op);
         // a captured burst (tunable graph) replays the launches of iterations k = 0..7 with their buffer roles baked in: the ring must return to its starting state after
@@ -722,8 +842,8 @@ int cg_run(lqcd_op_s* op, lqcd_spinor_s* x, lqcd_spinor_s* b, double eps, int ma
     }
     if (gexec) (void)hipGraphExecDestroy(gexec);
     if (graph) (void)hipGraphDestroy(graph);
-    if (!one_launch && (w.tgauge || (st == LQCD_OK && !converged))) {      // a window / an exhausted solve that stopped on an even iteration: complete x; temporal gauge: x back to the caller's basis
-        const int fs = cg_finish(op, x, w, st == LQCD_OK && !converged);
+    if (!one_launch && (w.tgauge || (st == LQCD_OK && (!converged || w.form == 3)))) {      // a window / an exhausted solve that stopped on an even iteration: complete x (residual ring: also behind the converging iteration); temporal gauge: x back to the caller's basis
+        const int fs = cg_finish(op, x, w, st == LQCD_OK && (!converged || w.form == 3));
         if (st == LQCD_OK) st = fs;
         if (st == LQCD_OK) { hipError_t e = hipStreamSynchronize(c->stream); if (e != hipSuccess) st = hip_fail(e, "cg flush", __FILE__, __LINE__); }
     }

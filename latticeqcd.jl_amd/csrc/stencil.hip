@@ -364,7 +364,9 @@ __global__ LQCD_DS_BOUNDS_FOLD void wilson_dirsplit_fold(KArgs k, HArgs h) { wil
 struct PipeArgs {
     const real2* gauge;       // the 18-real field, or the 12-real copy (template R12)
     const real2* clover;      // CINV instances (StencilCall::clover_on_hop): packed 6x6 blocks applied to the hop sum
-    real2* dst[2];            // out, or r in update mode (read and written)
+    real2* dst[2];            // out, or r in update mode (written; read through usrc)
+    const real2* usrc[2];     // scalar-addressing kernel, update mode: the centre read (StencilCall::upd_src; == dst: in place)
+    int rec;                  // scalar-addressing kernel: recurrence mode (StencilCall::upd_rec)
     const real2* in[2];
     const real2* xin[2];
     double* norm_partial;
@@ -801,6 +803,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
 #else
     constexpr bool LATE_R = DELTA || !R12;            // fp64: the instances that would spill at 3 waves per SIMD with the old r held across the hops
 #endif
+    constexpr bool RING = !DOT && !DW5 && !FOLD && !CINV;      // the instances with the separate update source and the recurrence mode (the others sit at their register caps)
     const size_t gpar = (size_t)a.nch * 4 * NL * 64;
     const PipeSite s = pipe_site<MU, NL>(a, vblock, lane);
     cd xv[3] = {mk(0, 0), mk(0, 0), mk(0, 0)}, rv[3] = {mk(0, 0), mk(0, 0), mk(0, 0)};
@@ -819,7 +822,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
         if constexpr (!CINV) load_z();
     } else if (!LATE_R && a.upd_scal) {    // (18-real and 12 + delta links: their extra words take these registers during the hops; the old r is requested behind them)
 #pragma unroll
-        for (int cc = 0; cc < 3; cc++) rv[cc] = ld(boff(s.p ? a.dst[1] : a.dst[0], s.own) + co12(3 * MU + cc));
+        for (int cc = 0; cc < 3; cc++) rv[cc] = ld(boff(RING ? (s.p ? a.usrc[1] : a.usrc[0]) : (s.p ? a.dst[1] : a.dst[0]), s.own) + co12(3 * MU + cc));
     }
     constexpr bool LATE_X = (LATE_R && !R12 && !DOT) || (CINV && DOT);      // all 18 reals, and the dot instances with the clover blocks in the epilogue: the diagonal term's load moves behind the hops as well
     if (!LATE_X && a.a != real(0.0)) {
@@ -959,7 +962,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
     }
     if constexpr (LATE_R && !DOT) if (a.upd_scal) {       // the LDS exchange and the barrier cover this load
 #pragma unroll
-        for (int cc = 0; cc < 3; cc++) rv[cc] = ld(boff(s.p ? a.dst[1] : a.dst[0], s.own) + co12(3 * MU + cc));
+        for (int cc = 0; cc < 3; cc++) rv[cc] = ld(boff(RING ? (s.p ? a.usrc[1] : a.usrc[0]) : (s.p ? a.dst[1] : a.dst[0]), s.own) + co12(3 * MU + cc));
     }
 #pragma unroll
     for (int j = 0; j < 12; j++) part[MU][j][lane] = mk2(acc[j].re, acc[j].im);
@@ -1046,9 +1049,15 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
             }
         } else if (a.upd_scal) {
             cd r = rv[cc];
-            r.re = fma(-al_upd, v.re, r.re); r.im = fma(-al_upd, v.im, r.im);
-            nrm = fma(r.re, r.re, nrm); nrm = fma(r.im, r.im, nrm);
-            st(dstp + co12(j), r);
+            if (RING && a.rec) {      // recurrence mode: s = v + beta s_old over s_old (al_upd = beta), |s|^2, the plain launch's store policy
+                r.re = fma(al_upd, r.re, v.re); r.im = fma(al_upd, r.im, v.im);
+                nrm = fma(r.re, r.re, nrm); nrm = fma(r.im, r.im, nrm);
+                if (a.nt_store) st_nt(dstp + co12(j), r); else st(dstp + co12(j), r);
+            } else {
+                r.re = fma(-al_upd, v.re, r.re); r.im = fma(-al_upd, v.im, r.im);
+                nrm = fma(r.re, r.re, nrm); nrm = fma(r.im, r.im, nrm);
+                st(dstp + co12(j), r);
+            }
         } else {
             nrm = fma(v.re, v.re, nrm); nrm = fma(v.im, v.im, nrm);
             if (a.nt_store) st_nt(dstp + co12(j), v); else st(dstp + co12(j), v);
@@ -1065,7 +1074,8 @@ __device__ __forceinline__ void dirsplit_s_block(const PipeArgs& a, real2 (*part
     }
     real al_upd = real(0);
     if (a.upd_scal) {
-        if (a.scal_w) {      // folded scalar step (several ranks): see update_alpha
+        if (!DOT && !DW5 && !FOLD && !CINV && a.rec) al_upd = (real)a.upd_scal[S_BETA];      // recurrence mode (the done flag was tested above: the in-place store makes it mandatory)
+        else if (a.scal_w) {      // folded scalar step (several ranks): see update_alpha
             const double rr = a.upd_scal[S_RR];
             const double al = rr / a.upd_scal[S_PQ];
             if (blockIdx.x == 0 && threadIdx.x == 0) { a.scal_w[S_ALPHA] = al; a.scal_w[S_RROLD] = rr; }
@@ -1762,6 +1772,8 @@ static PipeArgs make_pipe_args(lqcd_ctx_s* c, const KArgs& k, const StencilCall&
     PipeArgs a;
     a.gauge = k.gauge12 ? k.gauge12 : k.gauge;
     const bool upd = k.upd_scal != nullptr;
+    for (int p = 0; p < 2; p++) { a.usrc[p] = s.upd_src[p] ? (const real2*)s.upd_src[p] : k.upd[p]; }
+    a.rec = s.upd_rec;
     for (int p = 0; p < 2; p++) { a.dst[p] = upd ? k.upd[p] : k.out[p]; a.in[p] = k.in[p]; a.xin[p] = k.xin[p]; a.dotz[p] = k.dotz[p]; a.dotz2[p] = k.dotz2[p]; }
     a.dot_partial = k.dot_partial; a.dot_conj = k.dot_conj;
     a.clover = k.clover;
@@ -1887,6 +1899,11 @@ int launch_stencil_interior(lqcd_ctx_s* c, const StencilCall& s) {
     if (s.gauge12t && (kF32Build || s.kind != LQCD_WILSON || s.r != 1.0 || c->tun.dslash_variant != 1)) {      // (the tunables moved under an open CG session)
         set_error("stencil: temporal-gauge links are read by the 12-real Wilson r = 1 direction-split kernels only");
         return LQCD_ERR_UNSUPPORTED;
+    }
+    if (s.upd_rec || s.upd_src[0] || s.upd_src[1]) {      // the epilogues of the residual-ring CG exist in the scalar-addressing kernel alone (solvers.hip asks stencil_sdir_applies first)
+        const bool ok = !kF32Build && s.prec == 0 && s.upd_scal && s.upd[0] && s.upd[1] && !s.clover && !s.clover_on_hop && !s.dot_partial && !s.alpha_partials && s.dw_ls <= 1 && !s.fold &&
+                        !s.scal_w && (s.gauge12 || s.gauge12t || c->tun.dslash_s18) && stencil_sdir_applies(c, s.kind, s.r, false);
+        if (!ok) { set_error("stencil: a separate update source / the recurrence mode needs the scalar-addressing Wilson kernel (r = 1, no clover term, one unpartitioned GPU)"); return LQCD_ERR_UNSUPPORTED; }
     }
     if (use_dirsplit(c, s.kind, s.r)) {
         KArgs k = make_kargs(c, s, 64);
@@ -2192,6 +2209,12 @@ bool wilson_pipe_applies(lqcd_ctx_s* c, int kind, double r, int parity_mode, boo
 }
 // A full-lattice fp64 application that is handed the temporal-gauge links (StencilCall::gauge12t) runs the TG instances of the scalar-addressing kernel: asked by the
 // CG before it rotates anything.  (Launches that do not -- the small-lattice alpha_partials form -- read the unit links of the copy and compute the same bits.)
+// A full-lattice fp64 Wilson application (r = 1, no clover term) on one unpartitioned GPU runs the scalar-addressing direction-split kernel (12-real, 18-real, 12 + delta
+// or temporal-gauge instance): the kernel with the separate update source and the recurrence mode (StencilCall::upd_src / upd_rec)
+bool stencil_sdir_applies(lqcd_ctx_s* c, int kind, double r, bool clover) {
+    if (any_partitioned(c) || c->has_comm || c->tun.dslash_pipe != 2 || !(c->tun.gauge_recon == 12 || c->tun.dslash_s18)) return false;
+    return wilson_pipe_applies(c, kind, r, 2, clover);
+}
 bool stencil_tgauge_applies(lqcd_ctx_s* c, int kind, double r, bool clover) {
     if (any_partitioned(c) || c->tun.dslash_pipe != 2 || c->tun.gauge_recon != 12 || c->geom.L[3] < 2) return false;
     return wilson_pipe_applies(c, kind, r, 2, clover);
