@@ -396,6 +396,7 @@ extern "C" int lqcd_ctx_set_param(lqcd_ctx_t c, const char* key, int value) {
     if (!strcmp(key, "dslash_block")) ARGCHK(value == 64 || value == 128 || value == 256, "dslash_block must be 64, 128 or 256");
     if (!strcmp(key, "halo_stream_mode")) ARGCHK(value >= -1 && value <= 4, "halo_stream_mode must be -1 (timed once) or 0..4");
     if (!strcmp(key, "cg_rring")) ARGCHK(value == 0 || value == 2 || value == 4 || value == 8, "cg_rring must be 0 (off), 2, 4 or 8 (it divides the 8 iterations of a captured burst)");
+    if (!strcmp(key, "bicg_fused")) ARGCHK(value != 3, "bicg_fused must be 0, 1, 2 or 4 (3, the grid-barrier form, was measured slower and removed)");
     if (!strcmp(key, "halo_inject_us")) ARGCHK(value >= 0 && value <= 100000, "halo_inject_us: 0..100000");
     if ((!strcmp(key, "lazy_links") || !strcmp(key, "lazy_merge")) && !value) LQCHK(links_flush_of(c));      // switching to eager calls: what is recorded runs now
     *p = value;

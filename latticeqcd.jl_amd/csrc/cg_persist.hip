@@ -1,6 +1,6 @@
 // cg_persist.hip -- launch-bound lattices (BASELINE configs[1]: 8^4 staggered CG to 1e-10): the whole CG on D^+D in ONE launch.
 //
-// Replaces, for lattices of at most 256 chunks of 64 sites, the launch chain of solvers.hip cg_enqueue_iteration (cg_small: three dependent
+// Replaces, for lattices of at most 256 chunks of 64 sites, the launch chain of cg.hip cg_enqueue_iteration (cg_small: three dependent
 // ~5 us launches per iteration) behind the same entry point -- lqcd_solve_cg_DdagD, i.e. LatticeDiracOperators.jl's
 // solve_DinvX!(y, DdagD, x) -> cg (reference call site /root/reference/src/md/AbstractMD.jl:129 through calc_UdSfdU!).
 //

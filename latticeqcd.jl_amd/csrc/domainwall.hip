@@ -131,7 +131,7 @@ bool dw_batched_call(lqcd_op_s* op, double2* out, const double2* in, int dagger,
 }
 
 // x = (D5(mass)^+ D5(mass))^-1 b from a zero guess.
-// Where the five-dimensional launch applies (tunable dw_fused_cg): the fused iteration of the four-dimensional CG (solvers.hip cg_enqueue_iteration, its plain form) --
+// Where the five-dimensional launch applies (tunable dw_fused_cg): the fused iteration of the four-dimensional CG (cg.hip cg_enqueue_iteration, its Fused form) --
 //     t = D p with |t|^2 partials in the epilogue (one per workgroup = chunk x slice) ;  alpha = rr / |t|^2 in the reduction launch ;
 //     D^+ t in update mode: r -= alpha (D^+ t), |r|^2 partials, q = D^+D p never written ;  beta and the stopping test in the reduction launch ;
 //     x += alpha p, p = r + beta p in one pass

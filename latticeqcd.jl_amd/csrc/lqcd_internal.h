@@ -253,7 +253,7 @@ __device__ inline double sum_partials_small_nv(const double* __restrict__ partia
 __device__ inline double sum_partials_small(const double* __restrict__ partial, int n) { return sum_partials_small_nv(partial, n, 1, 0); }
 
 // ---------------------------------------------------------------- BiCGStab scalar steps (shared by the one-thread scalar kernels of blas.hip and the
-// prologues of the fused chain in solvers.hip: the same expressions, so the two forms produce the same bits)
+// prologues of the fused chain in bicgstab_eo.hip: the same expressions, so the two forms produce the same bits)
 struct c2 { double re, im; };
 __device__ inline c2 bicg_alpha(c2 rho, c2 r0v) {            // alpha = rho / <r0, v>
     const double d = r0v.re * r0v.re + r0v.im * r0v.im;
@@ -343,7 +343,7 @@ __device__ inline void cg_scalar_step(double* s, int op) {
         s[S_ITERS] += 1.0;
         if (rrn < s[S_EPS]) s[S_DONE] = 1.0;
     } else if (op == 7 || op == 9) {
-        // cg_fused = 3 (solvers.hip, residual ring): op 1 + alpha into the history of the pending batch; 9 opens a batch (the launch behind cg_batch_px)
+        // cg_fused = 3 (cg.hip, residual ring): op 1 + alpha into the history of the pending batch; 9 opens a batch (the launch behind cg_batch_px)
         if (s[S_DONE] != 0.0) { s[S_XDONE] = 1.0; return; }
         if (op == 9) s[S_BSTART] = s[S_ITERS];
         const double al = s[S_RR] / s[S_PQ];
@@ -528,7 +528,7 @@ struct Tunables {
                               // between two buffers): 9 instead of 10 spinor passes per iteration on average, identical iterates; K = 3..8 (round 5; 288 GB of HBM make
                               // the buffers free): a ring of K search-direction buffers, x += sum of K terms every K-th iteration -- (4 K + 1) / K update passes per
                               // iteration instead of 4.5 (K = 4: 4.25), the same iterates; 1 (default): 2 on an unpartitioned lattice, 8 on a partitioned one (measured:
-                              // solvers.hip cg_ring_wanted); 0: x every iteration
+                              // cg.hip cg_ring_wanted); 0: x every iteration
     int cg_persist = 1;       // staggered CG on an unpartitioned lattice of <= 256 chunks: the whole solve is ONE launch (cg_persist.hip), two grid-wide
                               // synchronisations per iteration instead of three dependent launches; 0: the cg_small launch chain
     int cg_small = 1;         // fused CG on an unpartitioned lattice with <= 1024 stencil workgroups: the two reduction launches of an iteration are folded
@@ -540,7 +540,7 @@ struct Tunables {
     int cg_skip_done = 1;     // fused CG: the first Dslash of an iteration checks the convergence flag as well (0: only the second does)
     int clover_transport = 0; // 1: build the clover sums by the plaquette-transport passes also on an unpartitioned lattice (tests)
     int stag_both = 0;            // 1: staggered split kernel issues the loads of both hops of a direction back to back (unpartitioned lattices)
-    int mixed_defer_x = 1;    // fp32 CG of the mixed-precision solver: x updated every second iteration with both search directions (solvers.hip cg_update_even/odd in fp32):
+    int mixed_defer_x = 1;    // fp32 CG of the mixed-precision solver: x updated every second iteration with both search directions (cg.hip cg_update_even/odd in fp32):
                               // 3 + 6 float streams per pair of iterations instead of 5 + 5, identical iterates
     int mixed_xfuse = 0;      // 1: fp32 site-pair solver forms x += alpha p in the epilogue of the update-mode D^+ (the update kernel then forms p only).  Bit-identical,
                               // measured SLOWER (50.4 vs 48.4 ms at 32^3x64: the six extra loads sit behind the barrier of a kernel that is at its register limit): off
@@ -557,17 +557,17 @@ struct Tunables {
     int variants_built = 0;   // read-only: dslash_variant >= 2 runs variant 1 (built without -DLQCD_VARIANTS)
 #endif
     int bicg_fused = 4;       // even-odd BiCGStab, plain Wilson r = 1 on an unpartitioned lattice: 4 [default, round 6] = 2 + the x / r update and the p update as ONE launch WITHOUT a
-                              // barrier: rho' and |r'|^2 from inner products that exist before r' does (solvers.hip bicgf_xrp_rec; <r0, t> from a second inner product in the dot
+                              // barrier: rho' and |r'|^2 from inner products that exist before r' does (bicgstab_eo.hip bicgf_xrp_rec; <r0, t> from a second inner product in the dot
                               // epilogue of every dot-mode kernel, Wilson-clover included) -- 6 launches, 12 vector passes instead of 14: 112.4 -> 106.0 us per iteration at 16^3x32, 20.9 -> 19.9 ms per
-                              // solve at 32^3x64; equal to form 2 up to the rounding of the two recurrences (no drift: rho - alpha <r0, v> = <r0, s> = 0 in every iteration); Wilson-clover 16^3x32: 186 -> 174 us per iteration.  3 [opt-in, round 6] = 2 + the x / r update and the p update as ONE launch
-                              // with a grid-wide barrier between them (6 launches per iteration; all <= 1024 workgroups resident) -- bit-identical and SLOWER (128.6 vs
-                              // 112.4 us per iteration at 16^3x32, profiles/r06_bicgstab_eo_chain.log: a barrier of 1024 workgroups costs more than the launch boundary it replaces); 1 = the inner products come from the epilogues of the Schur
+                              // solve at 32^3x64; equal to form 2 up to the rounding of the two recurrences (no drift: rho - alpha <r0, v> = <r0, s> = 0 in every iteration); Wilson-clover 16^3x32: 186 -> 174 us per iteration.  3 is refused: it was the same merge
+                              // with a grid-wide barrier instead of the recurrences, bit-identical to 2 and SLOWER (128.6 vs 112.4 us per iteration at 16^3x32,
+                              // profiles/r06_bicgstab_eo_chain.log: a barrier of 1024 workgroups costs more than the launch boundary it replaces), removed; 1 = the inner products come from the epilogues of the Schur
                               // operator's second hop (no dot-product passes), reductions and scalar steps as separate one-block launches; 2 = on lattices of
                               // <= 1024 chunks per parity the reductions and scalar steps also move into the prologues of the consumers (7 dependent launches per
                               // iteration instead of 17, identical iterates); 0 = the generic chain (what the clover / full-lattice solvers run)
     int clover_hop_s = 1;     // even-odd Wilson-clover solver: the hops with the inverse clover blocks on the hop sum run the scalar-addressing kernel (CINV instance of
                               // wilson_dirsplit_s) where it applies; 0: the plain direction-split kernel
-    int bicg_xrp_active = 0;  // read-only: the last even-odd BiCGStab solve ran the fused x / r / p launch -- 1: bicg_fused = 3 (grid barrier, every workgroup resident), 2: bicg_fused = 4 (recurrences)
+    int bicg_xrp_active = 0;  // read-only: 2: the last even-odd BiCGStab solve ran the merged x / r / p launch of bicg_fused = 4 (recurrences), 0: it did not
     int action_eo_solver = 1; // lqcd_fermi_action / lqcd_calc_UdSfdU, Wilson(-clover): X = (D^+D)^-1 eta through two even-odd BiCGStab solves (Y = D^-+ eta, X = D^-1 Y)
                               // instead of the CG on the normal equations (0: the reference's form); same stopping rule for the same residual (actions.hip)
     int lazy_links = 0;       // 1: the per-direction call triples of the reference's U_update! / P_update! (lqcd_link_exp -> lqcd_link_mul -> lqcd_link_copy,
@@ -1137,7 +1137,7 @@ double2* spinor_block(lqcd_spinor_s* s, int p);
 int gauge_ensure_recon12(lqcd_gauge_s* g);   // (re)builds the 12-real copy if the field changed; sets g->recon_ok
 int gauge_ensure_recon12d(lqcd_gauge_s* g);  // (re)builds the "12 + delta" copy; sets g->delta_ok
 int gauge_ensure_tgauge(lqcd_gauge_s* g);    // (re)builds G and the temporal-gauge copy of the 12-real links if the field changed; sets g->tgauge_ok
-int spinor_gauge_rotate(lqcd_ctx_s* c, const double2* gfix, double2* dst, const double2* src, int adjoint);   // solvers.hip: dst = G src / G^+ src on a full Wilson field (dst may be src)
+int spinor_gauge_rotate(lqcd_ctx_s* c, const double2* gfix, double2* dst, const double2* src, int adjoint);   // cg.hip: dst = G src / G^+ src on a full Wilson field (dst may be src)
 bool stencil_sdir_applies(lqcd_ctx_s* c, int kind, double r, bool clover);     // stencil.hip: a full-lattice fp64 application takes the scalar-addressing Wilson kernel (upd_src / upd_rec exist there)
 bool stencil_tgauge_applies(lqcd_ctx_s* c, int kind, double r, bool clover);   // stencil.hip: a full-lattice fp64 application with 12-real links would take the TG instances
 int plaquette_local_sum(lqcd_gauge_s* g, const double2* const ghost[4], double* sum);

@@ -135,7 +135,7 @@ __global__ __launch_bounds__(MB) void cg32_update_xp(const double* __restrict__ 
     }
 }
 
-// Deferred x update in fp32 (solvers.hip cg_update_even / cg_update_odd, same protocol): iteration k even: p_{k+1} = r + beta p_k into the
+// Deferred x update in fp32 (cg.hip cg_update_even / cg_update_odd, same protocol): iteration k even: p_{k+1} = r + beta p_k into the
 // OTHER buffer, x untouched, alpha_k kept in S_APREV (the iteration that converges completes x itself); k odd: x += alpha_{k-1} p_{k-1} +
 // alpha_k p_k in the order of two single updates (identical bits), p_{k+1} = r + beta p_k over the dead p_{k-1}.
 typedef float v4f32 __attribute__((ext_vector_type(4)));
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(MB) void cg32_update_p(const double* __restrict__ s
     }
 }
 
-// fp32 multi-shift update (solvers.hip ms_update_all on float4 = two elements): base system x += alpha p (optional), p = r + beta p, and
+// fp32 multi-shift update (multishift.hip ms_update_all on float4 = two elements): base system x += alpha p (optional), p = r + beta p, and
 // every active shift x_j += a_j p_j ; p_j = b_j p_j + z_j r in one pass; frozen shifts cost nothing
 __global__ __launch_bounds__(MB) void ms32_update_all(const double* __restrict__ sc, const double* __restrict__ ms, float4* const* __restrict__ ptr,
                                                        float4* __restrict__ x0, float4* __restrict__ p0, const float4* __restrict__ r, size_t n4, int ns) {
@@ -439,7 +439,7 @@ static int add_from_f32(lqcd_ctx_s* c, int layout, double2* y, const float2* x, 
 }
 
 // ---------------------------------------------------------------------------------- mixed-precision even-odd BiCGStab (plain Wilson)
-// M x = rhs on the even sites, M = 1 - k^2 H_eo H_oe:  outer fp64 defect correction around the fused chain of solvers.hip run on fp32 copies --
+// M x = rhs on the even sites, M = 1 - k^2 H_eo H_oe:  outer fp64 defect correction around the fused chain of bicgstab_eo.hip run on fp32 copies --
 //     r = rhs - M x (fp64) ;  while |r|^2 >= eps:  e ~ M^-1 (r / |r|) by the fp32 chain to a relative residual tol ;  x += |r| e ;  r = rhs - M x
 // The inner chain is the fp64 one (bicgstab_eo_wilson) in structure: the Schur operator's second hop forms the next inner product in its epilogue
 // (fp32 build of the direction-split kernel, double partials), reductions and scalar steps (double) run in the prologues of the three streaming
@@ -480,7 +480,7 @@ __global__ __launch_bounds__(UB) void bicgf32_s(BicgF a, float4* __restrict__ s,
     if (a.fold) { double t3[3]; block_sum_partials<3>(a.pin, a.pin_n, t3, a.pin_soa != 0); r0v.re = t3[0]; r0v.im = t3[1]; }
     else { r0v.re = a.sc[B_R0V]; r0v.im = a.sc[B_R0V + 1]; }
     const c2 al = bicg_alpha(rho, r0v);
-    if (a.pin3 && a.sc[B_UNSURE] != 0.0) {      // merged chain: the last update launch left the stopping test to the |r'|^2 it summed (solvers.hip bicgf_s)
+    if (a.pin3 && a.sc[B_UNSURE] != 0.0) {      // merged chain: the last update launch left the stopping test to the |r'|^2 it summed (bicgstab_eo.hip bicgf_s)
         double t1[1];
         block_sum_partials<1>(a.pin3, a.pin3_n, t1);
         if (blockIdx.x == 0 && threadIdx.x == 0) { a.sc[B_RES] = t1[0]; a.sc[B_RR] = t1[0]; }
@@ -575,7 +575,7 @@ __global__ __launch_bounds__(UB) void bicgf32_p(BicgF a, float4* __restrict__ p,
     for (int e = 0; e < 2; e++) { const size_t i = i0 + e * stride; if (i < n4) one(i, pv_[e], pr[e], pp[e]); }
     for (size_t i = i0 + 2 * stride; i < n4; i += stride) one(i, v[i], r[i], p[i]);
 }
-// the merged update launch of solvers.hip bicgf_xrp_rec on fp32 vectors: x += alpha p + omega s ; r = s - omega t ; p = r + beta (p - omega v) with
+// the merged update launch of bicgstab_eo.hip bicgf_xrp_rec on fp32 vectors: x += alpha p + omega s ; r = s - omega t ; p = r + beta (p - omega v) with
 // rho' = rho - alpha <r0, v> - omega <r0, t> and |r'|^2 = |s|^2 - |<t, s>|^2 / |t|^2 (double scalars from double sums of fp32 products)
 template <bool PAIR>
 __global__ __launch_bounds__(UB) void bicgf32_xrp_rec(BicgF a, float4* __restrict__ x, float4* __restrict__ r, float4* __restrict__ p, const float4* __restrict__ s,
@@ -690,11 +690,11 @@ static int inner_bicgstab_eo32(lqcd_op_s* op, const Eo32& m, size_t nh, int dg, 
     const int nbs = m.layout == 2 ? pair32_num_blocks(c) / 2 : (c->geom.Vh + 63) / 64;      // (dot instances: one workgroup per 64-site chunk, whatever dslash_pipe says)
     const int nbk = (int)std::min<size_t>(1024, (n4 + UB - 1) / UB);
     const bool fold = c->tun.bicg_fused >= 2 && nbs <= 1024;
-    // the merged update launch on the two recurrences (bicg_fused = 4, solvers.hip)
+    // the merged update launch on the two recurrences (bicg_fused = 4, bicgstab_eo.hip)
     const bool rec = c->tun.bicg_fused == 4;
     double* P0 = c->d_partial; double* P1 = P0 + (size_t)3 * nbs; double* P2 = P1 + nbk; double* P3 = P2 + (size_t)(rec ? 5 : 3) * nbs;
     const double* skip = c->d_scal + (B_DONE - S_DONE);
-    const bool soa = c->tun.bicg_dot_soa >= 2 || (c->tun.bicg_dot_soa == 1 && !fold && nbs > 1024);      // (solvers.hip: [value][workgroup] dot partials)
+    const bool soa = c->tun.bicg_dot_soa >= 2 || (c->tun.bicg_dot_soa == 1 && !fold && nbs > 1024);      // (bicgstab_eo.hip: [value][workgroup] dot partials)
     if (!pre_init) HIPCHK(hipMemsetAsync(m.x, 0, b32, c->stream));      // (pre_init: the conversion that made m.r also set x = 0, r0 = p = r)
     int it = 0, enq = 0;
     if (!cont) {
@@ -885,7 +885,7 @@ int bicgstab_eo_wilson_mixed(lqcd_op_s* op, lqcd_spinor_s& xe, lqcd_spinor_s* rh
 }
 
 // fp32 multi-shift CG: (A + sigma_j) e_j = rhs, j < ns, and A e = rhs if xbase is given; rhs in m.r with |rhs|^2 = 1, zero guesses.
-// The loop of inner_cg32 with the zeta recurrences (solvers.hip ms_zeta, double precision scalars) and one fused update pass.  A shift
+// The loop of inner_cg32 with the zeta recurrences (multishift.hip ms_zeta, double precision scalars) and one fused update pass.  A shift
 // is frozen once zeta_j^2 |r|^2 < eps2; without xbase the solve ends when every shift is frozen, with it when |r|^2 < eps2.
 static int inner_ms32(lqcd_op_s* op, const Mix32& m, float2* xbase, const std::vector<float2*>& xj, const std::vector<float2*>& pj,
                       const double* sigma, int ns, char* d_blk, size_t n, double eps2, int maxiter, int* iters, double* rr_out) {

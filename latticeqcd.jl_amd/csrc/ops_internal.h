@@ -1,4 +1,4 @@
-// ops_internal.h -- declarations shared by apply.hip / solvers.hip / actions.hip / bench_api.hip / mdom.hip (the former ops.hip).
+// ops_internal.h -- declarations shared by apply.hip / cg.hip / bicgstab.hip / bicgstab_eo.hip / multishift.hip / actions.hip / bench_api.hip / mdom.hip (the former ops.hip).
 #pragma once
 #include "lqcd_internal.h"
 
@@ -17,20 +17,24 @@ int make_full_call(lqcd_op_s* op, lqcd_spinor_s* out, lqcd_spinor_s* in, int dag
 void apply_bc(lqcd_ctx_s* c, const int bc[4]);
 void split_general_r(const StencilCall& s, StencilCall& s1, StencilCall& s2);   // Wilson r != 1 on a partitioned lattice = two r = 1 calls
 
-// solvers.hip
+// cg.hip
 constexpr int UB = 256;     // block size of the solvers' streaming kernels
+// what one CG iteration runs, chosen once by cg_setup (cg.hip cg_choose_form): Reference (cg_fused = 0: alpha = rr / <p, D^+D p>), NormFused (cg_fused = 1: |D p|^2
+// from the stencil), Fused (cg_fused >= 2, x updated every iteration), DeferX (the same with the x update deferred: two buffers or a ring), Small (reductions in the
+// consumers' prologues), RRing (residual ring).  Unset: a CgWork that cg_setup has not seen -- cg_enqueue_iteration refuses it.
+enum class CgForm { Unset, Reference, NormFused, Fused, DeferX, Small, RRing };
 struct CgWork {
     lqcd_spinor_s *r, *p, *q, *tmp;
     uint64_t pack_epoch = 0; // value of the context's halo_epoch right after that pack
     bool p_packed = false;   // partitioned lattice, halo_fuse bit 1: the send buffers hold the faces of the current search direction (packed by the last x/p update)
-    int form = -1;      // iteration form fixed at cg_setup (0 plain, 1 deferred x, 2 small-lattice, 3 residual ring): the tunables may change while a session is open
+    CgForm form = CgForm::Unset;      // fixed at cg_setup: the tunables may change while a session is open
     int k = 0;          // iterations enqueued so far (parity selects the p buffer when the x update is deferred: p_k lives in p for even k, in q for odd k)
-    int ring = 2;       // form 1: search-direction buffers in rotation (2: p, q; K > 2: p, q, more[0..K-3]; p_k lives in buffer k % K), fixed at cg_setup
+    int ring = 2;       // DeferX: search-direction buffers in rotation (2: p, q; K > 2: p, q, more[0..K-3]; p_k lives in buffer k % K), fixed at cg_setup
     lqcd_spinor_s* more[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     lqcd_spinor_s* buf(int j) const { return j == 0 ? p : j == 1 ? q : more[j - 2]; }
-    // form 3 (cg_fused = 3, solvers.hip "residual ring"): r_k lives in slot k % rring (slots: r, q, more[0..rring-3]), p in p, s = D p in tmp
+    // RRing (cg_fused = 3, cg.hip "residual ring"): r_k lives in slot k % rring (slots: r, q, more[0..rring-3]), p in p, s = D p in tmp
     int rring = 0;
-    bool flushed = false;    // form 3: the pending x terms have been applied (cg_flush_x); the window is over
+    bool flushed = false;    // RRing: the pending x terms have been applied (cg_flush_x); the window is over
     lqcd_spinor_s* slot(int j) const { return j == 0 ? r : j == 1 ? q : more[j - 2]; }
     // temporal gauge (decided once in cg_setup): x, r and the search directions are G times the caller's vectors and every stencil call of the iteration reads
     // the rotated links; cg_finish rotates x back
@@ -51,11 +55,34 @@ bool cg_gauge_moved(lqcd_op_s* op, const CgWork& w);      // temporal gauge: the
 bool cg_persist_ok(lqcd_op_s* op);
 int cg_persist_run(lqcd_op_s* op, lqcd_spinor_s* x, lqcd_spinor_s* b, CgWork& w, double eps, int maxiter, int* iters, double* rr, bool* converged, bool* gave_up);
 typedef std::function<int(double2* out, const double2* in)> ApplyFn;
+// CG for a Hermitian positive operator given as an enqueue function; x holds the initial guess, r, p, q: work of n elements
+int cg_generic(lqcd_ctx_s* c, const ApplyFn& A, size_t n, double2* x, const double2* b, double2* r, double2* p, double2* q, double eps,
+               int maxiter, int* iters, double* final_rr);
+// the fused tail of a CG iteration, x += alpha p ; p = r + beta p (device scalars; a no-op behind the converging iteration), on raw buffers
+int cg_launch_update_xp(lqcd_ctx_s* c, double2* x, double2* p, const double2* r, size_t n);
+
+// bicgstab.hip: x = A^-1 b for an operator given as an enqueue function; x holds the initial guess, w[0..5] = r, r0, p, v, s, t: work of n elements
+int bicgstab_core(lqcd_ctx_s* c, const ApplyFn& A, size_t n, double2* x, const double2* b, double2* const w[6], double eps, int maxiter, int* iters, double* final_rr);
+
+// multishift.hip
 // multi-shift coefficient step (zeta recurrences next to the CG scalars): d_ms = [sigma | zeta_{n-1} | zeta_n | a | b | z] (ns doubles each),
 // alpha_{n-1}, beta_{n-1}; stop_when_frozen raises S_DONE once every shift has converged (no unshifted solution wanted)
 int ms_zeta_launch(lqcd_ctx_s* c, double* d_ms, int ns, int stop_when_frozen);
 
-// ---- pieces shared by the fp64 (solvers.hip) and the mixed-precision (mixed.hip) even-odd BiCGStab chains
+#ifdef __HIPCC__
+// NT: streaming (non-temporal) access for fields that are not re-used before they fall out of every cache (cg.hip, multishift.hip; tunable nt_blas)
+typedef double v2dd __attribute__((ext_vector_type(2)));
+template <bool NT> __device__ inline double2 ldx(const double2* p) {
+    if constexpr (NT) { v2dd v = __builtin_nontemporal_load(reinterpret_cast<const v2dd*>(p)); double2 r; r.x = v.x; r.y = v.y; return r; }
+    else return *p;
+}
+template <bool NT> __device__ inline void stx(double2* p, double2 v) {
+    if constexpr (NT) { v2dd t = {v.x, v.y}; __builtin_nontemporal_store(t, reinterpret_cast<v2dd*>(p)); }
+    else *p = v;
+}
+#endif
+
+// ---- bicgstab_eo.hip, and the pieces its fp64 chain shares with the mixed-precision one (mixed.hip)
 #ifdef __HIPCC__
 template <int NV>
 __device__ inline void block_reduce_nv(double (&a)[NV], double* partial) {
@@ -114,11 +141,6 @@ int bicgstab_eo_wilson(lqcd_op_s* op, lqcd_spinor_s& xe, lqcd_spinor_s* rhs, lqc
 int bicgstab_eo_wilson_mixed(lqcd_op_s* op, lqcd_spinor_s& xe, lqcd_spinor_s* rhs, lqcd_spinor_s* const w[6], lqcd_spinor_s* to, int dg, double eps,
                              int maxiter, int* iters, double* final_rr, const double2* Ai = nullptr);
 
-// CG for a Hermitian positive operator given as an enqueue function (solvers.hip); x holds the initial guess, r, p, q: work of n elements
-int cg_generic(lqcd_ctx_s* c, const ApplyFn& A, size_t n, double2* x, const double2* b, double2* r, double2* p, double2* q, double eps,
-               int maxiter, int* iters, double* final_rr);
-// solvers.hip: the fused tail of a CG iteration, x += alpha p ; p = r + beta p (device scalars; a no-op behind the converging iteration), on raw buffers
-int cg_launch_update_xp(lqcd_ctx_s* c, double2* x, double2* p, const double2* r, size_t n);
 // domainwall.hip: the five-dimensional operator behind the entry points of the four-dimensional ones
 int dw_op_apply(lqcd_op_s* op, lqcd_spinor_s* out, lqcd_spinor_s* in, int dagger);
 int dw_op_apply_DdagD(lqcd_op_s* op, lqcd_spinor_s* out, lqcd_spinor_s* in);

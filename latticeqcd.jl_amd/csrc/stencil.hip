@@ -1900,7 +1900,7 @@ int launch_stencil_interior(lqcd_ctx_s* c, const StencilCall& s) {
         set_error("stencil: temporal-gauge links are read by the 12-real Wilson r = 1 direction-split kernels only");
         return LQCD_ERR_UNSUPPORTED;
     }
-    if (s.upd_rec || s.upd_src[0] || s.upd_src[1]) {      // the epilogues of the residual-ring CG exist in the scalar-addressing kernel alone (solvers.hip asks stencil_sdir_applies first)
+    if (s.upd_rec || s.upd_src[0] || s.upd_src[1]) {      // the epilogues of the residual-ring CG exist in the scalar-addressing kernel alone (cg.hip asks stencil_sdir_applies first)
         const bool ok = !kF32Build && s.prec == 0 && s.upd_scal && s.upd[0] && s.upd[1] && !s.clover && !s.clover_on_hop && !s.dot_partial && !s.alpha_partials && s.dw_ls <= 1 && !s.fold &&
                         !s.scal_w && (s.gauge12 || s.gauge12t || c->tun.dslash_s18) && stencil_sdir_applies(c, s.kind, s.r, false);
         if (!ok) { set_error("stencil: a separate update source / the recurrence mode needs the scalar-addressing Wilson kernel (r = 1, no clover term, one unpartitioned GPU)"); return LQCD_ERR_UNSUPPORTED; }

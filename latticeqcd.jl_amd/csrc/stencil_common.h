@@ -575,7 +575,7 @@ __device__ __forceinline__ void wilson_pack_site(const HArgs& k, const cd (&v)[1
     }
 }
 
-// pack blocks appended to the CG's x/p update launch (solvers.hip): thread -> (direction, side, slot, face site) like wilson_pack_dir, the new
+// pack blocks appended to the CG's x/p update launch (cg.hip): thread -> (direction, side, slot, face site) like wilson_pack_dir, the new
 // search direction p' = r + beta p at that site is formed in registers with the update kernel's own fma (same bits as the value the flat
 // part of the launch stores) and packed for the next D p.  k.in = p_k, k.upd = r (read only), pb = index of the pack block, npx = pack
 // blocks per (direction, side).

@@ -1,4 +1,4 @@
-"""The residual-ring form of the fp64 CG on D^+D (cg_fused = 3, solvers.hip cg_batch_px / cg_enqueue_rring) restated in numpy on the oracle's Wilson operator: no GPU.
+"""The residual-ring form of the fp64 CG on D^+D (cg_fused = 3, cg.hip cg_batch_px / cg_enqueue_rring) restated in numpy on the oracle's Wilson operator: no GPU.
 
 s_k = D p_k is formed by the recurrence s_{k+1} = D r_{k+1} + beta_k s_k and restarted from an exact D p at every batch boundary; the K residuals of a batch stay
 in a ring of K slots (r_k in slot k % K); alpha_k and beta_k go to histories; p and x are brought up to date once per K iterations by x += alpha_j p, p = r_{j+1} +

@@ -1,4 +1,4 @@
-"""The residual-ring form of the fp64 Wilson CG (cg_fused = 3, tunable cg_rring = K; solvers.hip cg_enqueue_rring / cg_batch_px, stencil.hip sdir_wave's separate
+"""The residual-ring form of the fp64 Wilson CG (cg_fused = 3, tunable cg_rring = K; cg.hip cg_enqueue_rring / cg_batch_px, stencil.hip sdir_wave's separate
 update source and recurrence mode).  D p is formed by s' = D r' + beta s from the residual D^+ has just written, p and x are brought up to date once per K iterations.
 Compared with cg_fused = 2 of the same library to the 1e-12 the project holds across cg_fused forms (tests/test_gpu_tgauge.py), iteration counts within +-1;
 bit for bit wherever the same launches run.  16.8.8.4 (cg_small = 0, cg_tgauge = 2: seam slices are half the lattice, 64 workgroups) and 16.16.16.32 (default

@@ -35,7 +35,7 @@ def test_cg_with_graph_replay_is_bit_identical(lq, name):
 @pytest.mark.parametrize("ring", [3, 5, 4, 8])
 def test_graph_replay_with_a_ring_of_search_direction_buffers(lq, ring):
     """a captured burst of 8 iterations bakes the buffer roles of k = 0..7 in; a ring of K buffers that does not divide 8 (3, 5, 6, 7) would not be back in
-    its starting state at the replay -- such a K takes the two-buffer form under graph = 1 (solvers.hip cg_setup).  Every K: the same bits as without the graph.
+    its starting state at the replay -- such a K takes the two-buffer form under graph = 1 (cg.hip cg_setup).  Every K: the same bits as without the graph.
     The lattice is large enough for the deferred-x form (more than 1024 stencil workgroups: no cg_small)."""
     L = (16, 16, 16, 16)
     U = lq.Initialize_Gaugefields(3, 0, *L, condition="hot", randomseed=5)

@@ -288,7 +288,7 @@ def test_evenodd_bicgstab_merged_update_on_the_recurrences(lq, orc, L, dagger, c
 def test_evenodd_bicgstab_fused_chain_is_bit_identical_to_the_unfolded_one(lq, orc):
     """Tunable bicg_fused.  1: the inner products of an iteration come from the epilogue of the Schur operator's second hop, reductions and scalar steps
     are separate one-block launches; 2 (default): on lattices of <= 1024 chunks per parity they run in the consumers' prologues -- 7 dependent launches
-    per iteration instead of 17; 3 (opt-in, round 6): the x / r and the p update as one launch with a grid barrier -- 6 (measured slower).  Same partials, same summation order, same scalar
+    per iteration instead of 17.  Same partials, same summation order, same scalar
     expressions: the same BITS in x, the same iteration count.  0 is
     the generic chain (separate dot-product kernels, other partial sums): equal to rounding.  All against the oracle's solution."""
     for L, dagger, csw in (((8, 8, 8, 16), False, 0.0), ((16, 16, 16, 32), True, 0.0), ((4, 4, 4, 8), False, 0.0), ((8, 8, 8, 16), True, 1.3), ((16, 16, 16, 32), False, 1.0)):
@@ -301,16 +301,17 @@ def test_evenodd_bicgstab_fused_chain_is_bit_identical_to_the_unfolded_one(lq, o
         b = lq.Fermionfields(lat, lq.WILSON)
         lq.gauss_distribution_fermion_(b, 112)
         out = {}
-        for mode in (3, 2, 1, 0):
+        for mode in (2, 1, 0):
             lat.set_param("bicg_fused", mode)
             x = b.similar()
             it, rr = lq.solve_DinvX_(x, Dd, b, return_info=True)
             out[mode] = (x.download(), it, rr)
             assert rr < 1e-19
-            assert lat.get_param("bicg_xrp_active") == (1 if mode == 3 else 0), mode      # the fused launch did run (every workgroup of it resident) / did not
+            assert lat.get_param("bicg_xrp_active") == 0, mode
+        with pytest.raises(lq.LQCDError):      # the grid-barrier form is gone
+            lat.set_param("bicg_fused", 3)
         lat.set_param("bicg_fused", 2)
         assert out[2][1] == out[1][1] and out[2][2] == out[1][2] and np.array_equal(out[2][0], out[1][0]), L      # folded == unfolded, bit for bit
-        assert out[3][1] == out[2][1] and out[3][2] == out[2][2] and np.array_equal(out[3][0], out[2][0]), L      # ... == the x / r / p update as one launch with a grid barrier (round 6)
         assert abs(out[0][1] - out[2][1]) <= 1 and rel_err(out[0][0], out[2][0]) < 1e-10
         if L[0] <= 8:
             Uh = U.download()
@@ -339,3 +340,46 @@ def test_evenodd_bicgstab_fused_chain_is_bit_identical_to_the_unfolded_one(lq, o
     lq.gauss_distribution_fermion_(b, 8)
     with pytest.raises(lq.NotConverged):
         lq.solve_DinvX_(x, D, b)
+
+
+@pytest.mark.parametrize("before,mid", [
+    ({"cg_small": 0, "cg_rring": 0, "cg_fused": 2, "cg_defer_x": 1}, {"cg_fused": 0}),      # deferred x; 3 is odd: the live p sits in the second buffer
+    ({"cg_small": 1, "cg_fused": 2}, {"cg_fused": 1}),                                      # small-lattice form
+    ({"cg_small": 0, "cg_fused": 3, "cg_rring": 4}, {"cg_rring": 0, "cg_fused": 2}),        # residual ring
+], ids=["deferred_x", "small", "residual_ring"])
+def test_the_iteration_form_of_an_open_cg_session_does_not_follow_the_tunables(lq, before, mid):
+    """The form a CG session iterates in is fixed when it is begun (cg.hip cg_setup / cg_choose_form): cg_fused / cg_rring changed between two windows of an
+    open session must not change a bit of x.  7 iterations in one window against 3 + 4 with the tunables changed in between, 16.8.8.4 (64 stencil workgroups)."""
+    L = (16, 8, 8, 4)
+    U = lq.Initialize_Gaugefields(3, 0, *L, condition="hot", randomseed=411)
+    lat = U.lattice
+    saved = {k: lat.get_param(k) for k in ("cg_persist", "cg_tgauge", "cg_small", "cg_rring", "cg_fused", "cg_defer_x")}
+    D = lq.Dirac_operator(U, None, {"Dirac_operator": "Wilson", "κ": KAPPA, "boundarycondition": (1, 1, 1, -1), "eps_CG": 1e-19, "MaxCGstep": 3000})
+    b = lq.Fermionfields(lat, lq.WILSON)
+    lq.gauss_distribution_fermion_(b, 412)
+
+    def run(windows):
+        lat.set_param("cg_persist", 0)
+        lat.set_param("cg_tgauge", 0)
+        for k, v in before.items():
+            lat.set_param(k, v)
+        x = b.similar()
+        lq.clear_fermion_(x)
+        ses = lq.CGSession(D, x, b)
+        try:
+            for i, n in enumerate(windows):
+                if i:
+                    for k, v in mid.items():
+                        lat.set_param(k, v)
+                ses.iterate(n)
+        finally:
+            ses.close()
+        return x.download()
+
+    try:
+        whole, split = run((7,)), run((3, 4))
+    finally:
+        for k, v in saved.items():
+            lat.set_param(k, v)
+    assert np.isfinite(whole).all() and np.abs(whole).max() > 0.0
+    assert np.array_equal(whole, split)

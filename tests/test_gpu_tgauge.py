@@ -1,4 +1,4 @@
-"""Wilson CG in temporal gauge (tunable cg_tgauge; fields.hip gauge_ensure_tgauge, stencil.hip wilson_dirsplit_s_tg, solvers.hip cg_setup / cg_finish).
+"""Wilson CG in temporal gauge (tunable cg_tgauge; fields.hip gauge_ensure_tgauge, stencil.hip wilson_dirsplit_s_tg, cg.hip cg_setup / cg_finish).
 The solve iterates on (U', G b, G x0) with U'_mu(n) = G(n) U_mu(n) G(n + mu)^+ and hands back G^+ x: the same Krylov space in another basis, so every
 result is compared with the cg_tgauge = 0 run of the same library -- relative max-norm 1e-12, one order over the 1e-13 operator bound for what accumulates
 over a window (the oracle pair of tests/test_tgauge_oracle.py sits at 2e-15).  cg_tgauge = 2 takes the path on small lattices; 16.16.16.32 (2048 stencil
