@@ -421,6 +421,20 @@ int lqcd_gauge_flow_observables(lqcd_gauge_t V, double obs[LQCD_FLOW_NOBS]);    
  * table receives nsteps/every rows [t, p, E_plaq, E_clov, Q_plaq, Q_clov, Q_impr] (row-major).  One device-to-host copy, at the end */
 int lqcd_gradient_flow_measure(lqcd_gauge_t V, double eps, int nsteps, int every, double* table);
 
+/* ---------------------------------------------------------------- R x T Wilson loops (src/measurements/measure_Wilsonloop.jl:71-126)
+ * The Wilson_loop measurement (Wilson_loop_measurement with Tmax = Rmax = 4, src/measurements/Measurement_set.jl:128-140) and calc_Wilson_loop(U, Lt, Ls):
+ * the loop [(mu, Ls), (4, Lt), (mu, -Ls), (4, -Lt)], mu = 1..3, normalised real(WL) / NV / 3 / NC.  Directions 0..3 = x, y, z, t; links are periodic
+ * and carry no boundary sign (as lqcd_gauge_polyakov).
+ *   S_mu,R(x) = U_mu(x) U_mu(x + mu) ... U_mu(x + (R-1) mu)   (mu = 0, 1, 2),      T_T(x) = U_3(x) U_3(x + t) ... U_3(x + (T-1) t)
+ *   W(R, T)   = 1/(9 V) sum_x sum_{mu = 0..2} Re tr[ S_mu,R(x) T_T(x + R mu) S_mu,R(x + T t)^+ T_T(x)^+ ]
+ * W(1, 1) is the mean plaquette of the three space-time planes only, not lqcd_gauge_plaquette.  table is row-major [Rmax][Tmax],
+ * table[(R-1) * Tmax + (T-1)] = W(R, T).  Valid: 1 <= Rmax <= min(Lx, Ly, Lz), 1 <= Tmax <= Lt; loops that wrap the lattice are legal and are computed as
+ * the formula says.  Anything outside that range or a null pointer: LQCD_ERR_ARG, table untouched.  A lattice with a partitioned direction (RCCL or the
+ * peer backend, LQCD_FORCE_PARTITION included) or an in-process PE grid: LQCD_ERR_UNSUPPORTED (the lines would cross ranks; lqcd_last_error says which).
+ * U is not modified and its version does not change; the line field and the other temporaries belong to the context.  One device-to-host copy, at the
+ * end; the table is bitwise reproducible from call to call (fixed-order reductions, no floating-point atomics). */
+int lqcd_gauge_wilson_loops(lqcd_gauge_t U, int Rmax, int Tmax, double* table);
+
 /* ---------------------------------------------------------------- quenched heatbath and overrelaxation (src/updates/heatbath.jl:1-44)
  * Plaquette action S_g = -(beta/3) sum_plaq Re tr U_p.  One heatbath sweep: mu = 0..3, even then odd sites, every link of that parity in place by
  * Cabibbo-Marinari over the SU(2) subgroups (1,2), (1,3), (2,3) (Kennedy-Pendleton / Creutz sampling); one overrelaxation (OR) sweep: the same order with

@@ -39,7 +39,8 @@ import LatticeDiracOperators: Dirac_operator, DdagD_operator, FermiAction, Initi
     AbstractFermionfields_4D
 
 export Initialize_HIPGaugefields, HIPLattice, HIPLink, HIPTALink, HIPFermion, HIPDirac, HIPFermiAction, reunitarize!, activate!, deactivate!,
-    HIPGradientflow, flow_observables, energy_density, topological_charge, gradient_flow_measure, HIPHeatbath, heatbath_measure
+    HIPGradientflow, flow_observables, energy_density, topological_charge, gradient_flow_measure, HIPHeatbath, heatbath_measure,
+    wilson_loops, calc_Wilson_loop
 
 const LIB = get(ENV, "LQCD_HIP_LIB", joinpath(@__DIR__, "..", "latticeqcd.jl_amd", "csrc", "liblqcd_hip.so"))
 
@@ -353,6 +354,16 @@ function gradient_flow_measure(U::Vector{HIPLink}, eps::Real, numflow::Integer, 
     check(ccall((:lqcd_gradient_flow_measure, LIB), Cint, (Ptr{Cvoid}, Float64, Cint, Cint, Ptr{Float64}), whole(U).h, Float64(eps), numflow, every, tab))
     return [tab[j, i] for i = 1:nrows, j = 1:7]
 end
+
+# the Wilson_loop measurement (src/measurements/measure_Wilsonloop.jl:71-126): W[R, T] = 1/(9 V) sum_x sum_mu Re tr of the R x T loop in the three
+# space-time planes, R = 1..Rmax, T = 1..Tmax, in one call (lqcd_gauge_wilson_loops; refused on a partitioned lattice)
+function wilson_loops(U::Vector{HIPLink}, Rmax::Integer, Tmax::Integer)
+    tab = zeros(Float64, Tmax, Rmax)       # column-major Tmax x Rmax = the C side's row-major Rmax x Tmax
+    check(ccall((:lqcd_gauge_wilson_loops, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}), whole(U).h, Rmax, Tmax, tab))
+    return [tab[t, r] for r = 1:Rmax, t = 1:Tmax]
+end
+# calc_Wilson_loop(U, Lt, Ls) (measure_Wilsonloop.jl:71-82), the time extent first: real(WL) / NV / 3 / NC of the Ls x Lt loop
+calc_Wilson_loop(U::Vector{HIPLink}, Lt, Ls) = wilson_loops(U, Ls, Lt)[Ls, Lt]
 
 # the quenched heatbath (src/updates/heatbath.jl): Heatbathupdate builds `Heatbath(U, β, ITERATION_MAX = ITERATION_MAX)` (heatbath.jl:27) and update!
 # (:35-43) calls `heatbath!(U, hb)` and `overrelaxation!(U, hb)` -- Gaugefields generics, imported above and extended here for the binding's links.

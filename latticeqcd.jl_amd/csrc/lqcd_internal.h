@@ -827,6 +827,11 @@ struct lqcd_ctx_s {
     size_t flow_tab_n = 0;
     double* hb_tab = nullptr;           // heatbath (heatbath.hip): word 0 = draws that ran out of trials, then the plaquette sums of a measured run
     size_t hb_tab_n = 0;
+    double2* wl_s = nullptr;            // Wilson loops (wilsonloop.hip): the space-like lines S_mu,R, gauge-shaped (slots 0..2), allocated on first use
+    double* wl_partial = nullptr;       // ... block partials [Tmax][3][blocks] of one R
+    size_t wl_partial_n = 0;
+    double* wl_tab = nullptr;           // ... device table of the Rmax x Tmax sums
+    size_t wl_tab_n = 0;
     double2* clover_q[2] = {};          // clover sums / transport ping-pong, six 3x3 matrices per site (clover.hip)
     double2* clover_ext = nullptr;      // halo-extended links + Lambda matrices of the partitioned clover force, and its face buffers
     size_t clover_ext_bytes = 0;

@@ -14,6 +14,7 @@ Reference call sites mirrored (paths relative to /root/reference):
   calculate_Plaquette                                           src/system/lqcd.jl:187-193
   Gradientflow, flow!, Energy_density, Topological_charge       src/system/lqcd.jl:95-100,149-164
   Heatbath, heatbath!, overrelaxation!, Heatbathupdate, update!  src/updates/heatbath.jl:1-44, src/updates/AbstractUpdate.jl:59-108
+  calc_Wilson_loop, Wilson_loop_measurement                     src/measurements/measure_Wilsonloop.jl:71-126, src/measurements/Measurement_set.jl:128-140
 
 Host arrays are numpy complex128, C order, with the memory image of the Julia arrays:
   gauge U[mu,t,z,y,x,b,a], Wilson psi[s,t,z,y,x,c], staggered psi[t,z,y,x,c]   (local sub-lattice of this rank).
@@ -343,6 +344,54 @@ def flow_scales(table, energy="E_clov", target=0.3):
     W = tm * np.diff(F) / np.diff(t)
     w2 = _crossing(tm, W, target)
     return t0, float(np.sqrt(w2)) if w2 == w2 else float("nan")
+
+
+# ---- R x T Wilson loops (src/measurements/measure_Wilsonloop.jl:71-126; include/lqcd_hip.h "R x T Wilson loops", csrc/wilsonloop.hip)
+def wilson_loops(U, Rmax=4, Tmax=4):
+    """The table W[R-1, T-1] = W(R, T), R = 1..Rmax, T = 1..Tmax, of the planar Wilson loops in the three space-time planes
+    (lqcd_gauge_wilson_loops): 1/(9 V) sum_x sum_mu Re tr of the R x T loop.  Not available on a partitioned lattice."""
+    tab = np.zeros((int(Rmax), int(Tmax)), dtype=np.float64)
+    check(_l.lib().lqcd_gauge_wilson_loops(U._h, int(Rmax), int(Tmax), tab.ctypes.data_as(C.POINTER(C.c_double))))
+    return tab
+
+
+def calc_Wilson_loop(U, Lt, Ls):
+    """calc_Wilson_loop(U, Lt, Ls) (measure_Wilsonloop.jl:71-82), the time extent first: the Ls x Lt loop, real(WL) / NV / 3 / NC."""
+    return float(wilson_loops(U, int(Ls), int(Lt))[int(Ls) - 1, int(Lt) - 1])
+
+
+class Wilson_loop_measurement:
+    """Wilson_loop_measurement(U; Tmax = 4, Rmax = 4) (src/measurements/Measurement_set.jl:128-140): measure(U) returns the Rmax x Tmax table."""
+
+    def __init__(self, U=None, Rmax=4, Tmax=4):
+        self.Rmax = int(Rmax)
+        self.Tmax = int(Tmax)
+
+    def measure(self, U):
+        return wilson_loops(U, self.Rmax, self.Tmax)
+
+
+def _log_positive(r):
+    r = np.asarray(r, dtype=np.float64)
+    out = np.full(r.shape, np.nan)
+    ok = np.isfinite(r) & (r > 0)
+    out[ok] = np.log(r[ok])
+    return out
+
+
+def static_potential(table):
+    """a V(R; T) = log(W(R, T) / W(R, T + 1)) from a wilson_loops table, shape (Rmax, Tmax - 1); NaN where the ratio is not positive."""
+    W = np.asarray(table, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return _log_positive(W[:, :-1] / W[:, 1:])
+
+
+def creutz_ratios(table):
+    """chi(R, T) = -log[W(R, T) W(R-1, T-1) / (W(R-1, T) W(R, T-1))] for R, T >= 2 from a wilson_loops table, shape (Rmax - 1, Tmax - 1);
+    NaN where the ratio is not positive."""
+    W = np.asarray(table, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return -_log_positive(W[1:, 1:] * W[:-1, :-1] / (W[:-1, 1:] * W[1:, :-1]))
 
 
 # ---- quenched heatbath and overrelaxation (src/updates/heatbath.jl; include/lqcd_hip.h "quenched heatbath", csrc/heatbath.hip)
