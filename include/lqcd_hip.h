@@ -435,6 +435,32 @@ int lqcd_gradient_flow_measure(lqcd_gauge_t V, double eps, int nsteps, int every
  * end; the table is bitwise reproducible from call to call (fixed-order reductions, no floating-point atomics). */
 int lqcd_gauge_wilson_loops(lqcd_gauge_t U, int Rmax, int Tmax, double* table);
 
+/* ---------------------------------------------------------------- meson correlators from point-source propagators (src/measurements/unusedfiles/measure_Pion_correlator.jl)
+ * Directions 0..3 = x, y, z, t; gLt is the GLOBAL time extent.  gamma_mu and gamma_5 are the matrices the operator is built with, each a
+ * permutation with phases in {+-1, +-i}.  The 16 channels are Gamma_n = gamma_x^n0 gamma_y^n1 gamma_z^n2 gamma_t^n3, n = n0 + 2 n1 + 4 n2 + 8 n3 = 0..15
+ * (Gamma_0 = 1: scalar, Gamma_1, 2, 4 = gamma_x, y, z: the rho, Gamma_8 = gamma_t, Gamma_15 = gamma_5: the pion).  For a point source at the
+ * global site x0, S(x)[alpha a, beta b] is component (sink spin alpha, sink colour a) of the solution of D S = delta_{x,x0} delta_{alpha beta} delta_{ab}, and
+ *     C_n(t) = sum_{x: x_t = t} Re tr_{spin,colour}[ Gamma_n S(x) Gamma_n^+ gamma_5 S(x)^+ gamma_5 ]
+ * with t the absolute global time coordinate (the reference's Cpi[t]), not the distance from the source.  C_15(t) = sum |S|^2 is the reference's Pion_correlator
+ * (measure_Pion_correlator.jl:283).  Tables are row-major [16][gLt], table[n * gLt + t] = C_n(t).
+ * A null pointer, a bad ncol, a src outside the global lattice, or columns that are not FULL Wilson fields of one context: LQCD_ERR_ARG, outputs untouched.  A staggered
+ * operator in lqcd_meson_correlators, a Domainwall operator, or an in-process PE grid: LQCD_ERR_UNSUPPORTED (lqcd_last_error says which).  A solve that does not converge
+ * returns its LQCD_ERR_NOT_CONVERGED and leaves the table untouched.  The contraction is site-local, so every entry is collective on a partitioned lattice (RCCL and the
+ * peer backend) and every rank gets the same values: a rank sums its own time slices into a zero-filled device table at slot origin[3] + t, one all-reduce of the device table
+ * follows.  One device-to-host copy, at the end; fixed-order reductions and no floating-point atomics, so two calls give the same bits.  The links and the operator are not
+ * modified; the five work spinors (source + four solutions) come from the context's scratch pool and, like the partial-sum buffers, are reused between calls. */
+#define LQCD_MESON_NCHAN 16
+/* out[t] = sum over the sites of global time slice t and all components of |s|^2; FULL 4-D Wilson or staggered spinor */
+int lqcd_spinor_norm2_timeslices(lqcd_spinor_t s, double* out /* [gLt] */);
+/* cols[4*b + beta]: the Wilson solution for source colour b, source spin beta (the reference's icum order, colour-major); ncol = 4, 8 or 12;
+ * table[n * gLt + t] = C_n(t) summed over the ncol/4 colour blocks given */
+int lqcd_meson_contract(const lqcd_spinor_t* cols, int ncol, double* table /* [16][gLt] */);
+/* 12 point-source solves at global site src + the contraction, resident; Wilson and Wilson-clover operators (lqcd_solve_bicgstab_eo, zero guess).  One source colour
+ * (four spin columns) is solved, contracted and accumulated on the device at a time: twelve columns are never held */
+int lqcd_meson_correlators(lqcd_op_t op, const int src[4], double eps, int maxiter, double* table /* [16][gLt] */, int* iters /* [12] or NULL */);
+/* the reference's Pion_correlator: Wilson/clover = row 15 of the above; staggered = 3 colour solves (CG on D^+D, then D^+), C(t) = sum |G|^2 */
+int lqcd_pion_correlator(lqcd_op_t op, const int src[4], double eps, int maxiter, double* C /* [gLt] */, int* iters /* [12] or [3] or NULL */);
+
 /* ---------------------------------------------------------------- quenched heatbath and overrelaxation (src/updates/heatbath.jl:1-44)
  * Plaquette action S_g = -(beta/3) sum_plaq Re tr U_p.  One heatbath sweep: mu = 0..3, even then odd sites, every link of that parity in place by
  * Cabibbo-Marinari over the SU(2) subgroups (1,2), (1,3), (2,3) (Kennedy-Pendleton / Creutz sampling); one overrelaxation (OR) sweep: the same order with

@@ -40,7 +40,7 @@ import LatticeDiracOperators: Dirac_operator, DdagD_operator, FermiAction, Initi
 
 export Initialize_HIPGaugefields, HIPLattice, HIPLink, HIPTALink, HIPFermion, HIPDirac, HIPFermiAction, reunitarize!, activate!, deactivate!,
     HIPGradientflow, flow_observables, energy_density, topological_charge, gradient_flow_measure, HIPHeatbath, heatbath_measure,
-    wilson_loops, calc_Wilson_loop
+    wilson_loops, calc_Wilson_loop, meson_correlators, pion_correlator, Pion_correlator_measurement, measure
 
 const LIB = get(ENV, "LQCD_HIP_LIB", joinpath(@__DIR__, "..", "latticeqcd.jl_amd", "csrc", "liblqcd_hip.so"))
 
@@ -711,6 +711,48 @@ rational_apply!(y::HIPFermion, D::HIPDirac, x::HIPFermion, a0, res::Vector{Float
 rational_force!(G::Vector{HIPLink}, D::HIPDirac, φ::HIPFermion, res::Vector{Float64}, poles::Vector{Float64}) =
     check(ccall((:lqcd_rational_force, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Float64, Cint, Ptr{Cint}),
                 D.h, whole(G).h, φ.h, length(res), res, poles, D.eps_CG, D.MaxCGstep, C_NULL))
+
+# ---- meson correlators (src/measurements/unusedfiles/measure_Pion_correlator.jl; include/lqcd_hip.h "meson correlators")
+# The 16 x gLt table of a point source at the global site src (0-based x, y, z, t): 12 even-odd BiCGStab solves under D's stopping rule and the contraction, resident.
+# Row n is Gamma_n = gamma_x^n0 gamma_y^n1 gamma_z^n2 gamma_t^n3, n = n0 + 2 n1 + 4 n2 + 8 n3; tab[n + 1, t + 1] = C_n(t), t the absolute time coordinate.
+function meson_correlators(D::HIPDirac, src = (0, 0, 0, 0))
+    gLt = lattice(D.U).L[4]
+    tab = zeros(Float64, gLt, 16)          # column-major gLt x 16 = the C side's row-major [16][gLt]
+    check(ccall((:lqcd_meson_correlators, LIB), Cint, (Ptr{Cvoid}, Ptr{Cint}, Float64, Cint, Ptr{Float64}, Ptr{Cint}),
+                D.h, Cint[src...], D.eps_CG, D.MaxCGstep, tab, C_NULL))
+    return [tab[t, n] for n = 1:16, t = 1:gLt]
+end
+# Cpi[t] of the Pion_correlator measurement: Wilson / Wilson-clover = row 15 of the table above, staggered = three colour solves, C(t) = sum |G|^2
+function pion_correlator(D::HIPDirac, src = (0, 0, 0, 0))
+    Cpi = zeros(Float64, lattice(D.U).L[4])
+    check(ccall((:lqcd_pion_correlator, LIB), Cint, (Ptr{Cvoid}, Ptr{Cint}, Float64, Cint, Ptr{Float64}, Ptr{Cint}),
+                D.h, Cint[src...], D.eps_CG, D.MaxCGstep, Cpi, C_NULL))
+    return Cpi
+end
+# Pion_correlator_measurement(U; fermiontype, mass, κ, r, eps_CG, MaxCGstep, BoundaryCondition) (measure_Pion_correlator.jl:14-29, same defaults) and measure
+struct Pion_correlator_measurement
+    D::HIPDirac
+end
+function Pion_correlator_measurement(U::Vector{HIPLink}; fermiontype = "Staggered", mass = 0.1, Nf = 2, κ = 1, r = 1, eps_CG = 1e-14, MaxCGstep = 3000,
+                                     BoundaryCondition = nothing, kwargs...)
+    bc = BoundaryCondition === nothing ? [1, 1, 1, -1] : BoundaryCondition
+    params = Dict{String,Any}("eps_CG" => eps_CG, "MaxCGstep" => MaxCGstep, "boundarycondition" => bc)
+    if fermiontype == "Staggered"
+        params["Dirac_operator"] = "staggered"
+        params["mass"] = mass
+        x = Initialize_pseudofermion_fields(U[1], "staggered")
+    elseif fermiontype == "Wilson"
+        params["Dirac_operator"] = "Wilson"
+        params["κ"] = κ
+        params["r"] = r
+        params["method_CG"] = "bicgstab_evenodd"
+        x = Initialize_pseudofermion_fields(U[1], "Wilson", nowing = true)
+    else
+        error("fermion type $fermiontype is not supported in Pion_correlator_measurement")
+    end
+    return Pion_correlator_measurement(Dirac_operator(U, x, params))
+end
+measure(m::Pion_correlator_measurement, U::Vector{HIPLink}) = pion_correlator(m.D(U))
 
 # ---- fused four-direction forms of the MD step (one kernel each; what a maintainer would call from a specialised
 # P_update!(U::Vector{HIPLink}, p, ϵ, md) / U_update! method to skip the per-direction temporaries)

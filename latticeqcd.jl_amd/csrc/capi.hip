@@ -284,6 +284,7 @@ extern "C" int lqcd_ctx_destroy(lqcd_ctx_t c) {
     (void)hipFree(c->flow_x); (void)hipFree(c->flow_partial); (void)hipFree(c->flow_tab);
     (void)hipFree(c->hb_tab);
     (void)hipFree(c->wl_s); (void)hipFree(c->wl_partial); (void)hipFree(c->wl_tab);
+    (void)hipFree(c->ms_partial); (void)hipFree(c->ms_tab);
     (void)hipFree(c->clover_ext); (void)hipFree(c->clover_ext_buf[0]); (void)hipFree(c->clover_ext_buf[1]);
     if (c->has_comm && !c->peer.on) { ncclCommDestroy(c->comm); ncclCommDestroy(c->comm_red); }
     comm_teardown(c);      // the peer-mapped backend's windows (comm.hip)

@@ -832,6 +832,10 @@ struct lqcd_ctx_s {
     size_t wl_partial_n = 0;
     double* wl_tab = nullptr;           // ... device table of the Rmax x Tmax sums
     size_t wl_tab_n = 0;
+    double* ms_partial = nullptr;       // meson correlators (meson.hip): workgroup partials [channel][t][workgroup] of one contraction launch
+    size_t ms_partial_n = 0;
+    double* ms_tab = nullptr;           // ... device table [16][gLt] of the time-slice sums
+    size_t ms_tab_n = 0;
     double2* clover_q[2] = {};          // clover sums / transport ping-pong, six 3x3 matrices per site (clover.hip)
     double2* clover_ext = nullptr;      // halo-extended links + Lambda matrices of the partitioned clover force, and its face buffers
     size_t clover_ext_bytes = 0;

@@ -15,6 +15,7 @@ Reference call sites mirrored (paths relative to /root/reference):
   Gradientflow, flow!, Energy_density, Topological_charge       src/system/lqcd.jl:95-100,149-164
   Heatbath, heatbath!, overrelaxation!, Heatbathupdate, update!  src/updates/heatbath.jl:1-44, src/updates/AbstractUpdate.jl:59-108
   calc_Wilson_loop, Wilson_loop_measurement                     src/measurements/measure_Wilsonloop.jl:71-126, src/measurements/Measurement_set.jl:128-140
+  Pion_correlator_measurement, Chiral_condensate_measurement    src/measurements/unusedfiles/measure_Pion_correlator.jl, measure_chiral_condensate.jl:164-204
 
 Host arrays are numpy complex128, C order, with the memory image of the Julia arrays:
   gauge U[mu,t,z,y,x,b,a], Wilson psi[s,t,z,y,x,c], staggered psi[t,z,y,x,c]   (local sub-lattice of this rank).
@@ -796,6 +797,119 @@ def apply_inverse_power_(y, A, x, alpha, lam_min, lam_max, tol=1e-10):
         add_fermion_(y, float(r), xk)
         xk.close()
     return it
+
+
+# ------------------------------------------------------------------------------------ fermionic measurements
+# meson correlators (src/measurements/unusedfiles/measure_Pion_correlator.jl; include/lqcd_hip.h "meson correlators", csrc/meson.hip) and the chiral
+# condensate (src/measurements/unusedfiles/measure_chiral_condensate.jl:164-204)
+def _channel_name(n):
+    return "".join(g for mu, g in enumerate(("gx", "gy", "gz", "gt")) if (n >> mu) & 1) or "1"
+
+
+# row n of a meson table is Gamma_n = gamma_x^n0 gamma_y^n1 gamma_z^n2 gamma_t^n3, n = n0 + 2 n1 + 4 n2 + 8 n3: "1" the scalar, "gx", "gy", "gz" the rho,
+# "gxgygzgt" = gamma_5 the pion
+MESON_CHANNELS = tuple(_channel_name(n) for n in range(16))
+
+
+def _global_Lt(lattice):
+    return int(lattice.L[3])
+
+
+def norm2_timeslices(x):
+    """out[t] = sum of |x|^2 over the sites of GLOBAL time slice t and all components (lqcd_spinor_norm2_timeslices); every rank gets all slices."""
+    out = np.zeros(_global_Lt(x.lattice), dtype=np.float64)
+    check(_l.lib().lqcd_spinor_norm2_timeslices(x._h, _ptr(out)))
+    return out
+
+
+def meson_contract(cols):
+    """table[n, t] = C_n(t) of 4, 8 or 12 resident Wilson columns, cols[4 b + beta] = the solution for source colour b, source spin beta
+    (lqcd_meson_contract): the sum over the colour blocks given."""
+    cols = list(cols)
+    if not cols:
+        raise LQCDError(_l.ERR_ARG, "meson_contract: no columns")
+    tab = np.zeros((16, _global_Lt(cols[0].lattice)), dtype=np.float64)
+    arr = (C.c_void_p * len(cols))(*[c._h for c in cols])
+    check(_l.lib().lqcd_meson_contract(arr, len(cols), _ptr(tab)))
+    return tab
+
+
+def meson_correlators(D, src=(0, 0, 0, 0), return_info=False):
+    """The 16 x gLt table of a point source at the global site src = (x, y, z, t): 12 even-odd BiCGStab solves under D's stopping rule
+    (D.eps_CG, D.MaxCGstep) and the contraction, resident (lqcd_meson_correlators).  Wilson and Wilson-clover operators."""
+    tab = np.zeros((16, _global_Lt(D.lattice)), dtype=np.float64)
+    its = (C.c_int * 12)()
+    check(_l.lib().lqcd_meson_correlators(D._h, _l.i4(src), C.c_double(D.eps_CG), int(D.MaxCGstep), _ptr(tab), its))
+    return (tab, list(its)) if return_info else tab
+
+
+def pion_correlator(D, src=(0, 0, 0, 0), return_info=False):
+    """Cpi[t] of the reference's Pion_correlator (lqcd_pion_correlator): Wilson / Wilson-clover = row 15 of meson_correlators, staggered = three colour solves."""
+    Cpi = np.zeros(_global_Lt(D.lattice), dtype=np.float64)
+    its = (C.c_int * 12)()
+    check(_l.lib().lqcd_pion_correlator(D._h, _l.i4(src), C.c_double(D.eps_CG), int(D.MaxCGstep), _ptr(Cpi), its))
+    return (Cpi, list(its)[:12 if D.kind == WILSON else 3]) if return_info else Cpi
+
+
+def _measurement_operator(U, who, fermiontype, mass, κ, r, L5, M, eps_CG, MaxCGstep, BoundaryCondition, kappa=None):
+    """The operator the reference's fermionic measurements build from their keywords (measure_Pion_correlator.jl:14-85, measure_chiral_condensate.jl:17-82)."""
+    bc = (1, 1, 1, -1) if BoundaryCondition is None else tuple(BoundaryCondition)
+    params = {"eps_CG": eps_CG, "MaxCGstep": MaxCGstep, "boundarycondition": bc}
+    if fermiontype == "Staggered":
+        params.update({"Dirac_operator": "staggered", "mass": mass})
+    elif fermiontype == "Wilson":
+        params.update({"Dirac_operator": "Wilson", "κ": κ if kappa is None else kappa, "r": r, "method_CG": "bicgstab_evenodd"})
+    elif fermiontype == "Domainwall":
+        raise LQCDError(_l.ERR_UNSUPPORTED, f"{who}: Domainwall measurements are not supported")
+    else:
+        raise LQCDError(_l.ERR_UNSUPPORTED, f"fermion type {fermiontype} is not supported in {who}")
+    return Dirac_operator(U, None, params)
+
+
+class Pion_correlator_measurement:
+    """Pion_correlator_measurement(U; fermiontype, mass, Nf, κ, r, L5, M, eps_CG, MaxCGstep, BoundaryCondition) (measure_Pion_correlator.jl:14-29, same
+    defaults): measure(U) returns Cpi[t], t the absolute time coordinate, for a point source at the origin (or `src`)."""
+
+    def __init__(self, U, fermiontype="Staggered", mass=0.1, Nf=2, κ=1, r=1, L5=2, M=-1, eps_CG=1e-14, MaxCGstep=3000, BoundaryCondition=None,
+                 kappa=None, src=(0, 0, 0, 0), **kw):
+        self.D = _measurement_operator(U, "Pion_correlator_measurement", fermiontype, mass, κ, r, L5, M, eps_CG, MaxCGstep, BoundaryCondition, kappa)
+        self.src = tuple(int(v) for v in src)
+
+    def measure(self, U):
+        return pion_correlator(self.D(U), self.src)
+
+
+class Chiral_condensate_measurement:
+    """Chiral_condensate_measurement(U; fermiontype, mass, Nf, κ, r, eps_CG, MaxCGstep, BoundaryCondition, Nr) (measure_chiral_condensate.jl:17-33, same
+    defaults) and measure (:164-204): per noise vector Z4_distribution_fermi!(r), clear_fermion!(p), solve_DinvX!(p, D, r), dot(r, p);
+    the value is real(sum / Nr) / NV * factor, factor = Nf / 4 (staggered) or 1 (Wilson).  Noise vector ir is drawn with seed randomseed + ir.
+    Staggered D^-1 = D' (D'D)^-1 by CG, Wilson by the even-odd BiCGStab."""
+
+    def __init__(self, U, fermiontype="Staggered", mass=0.1, Nf=2, κ=1, r=1, L5=2, M=-1, eps_CG=1e-14, MaxCGstep=3000, BoundaryCondition=None,
+                 Nr=10, kappa=None, randomseed=113, **kw):
+        self.D = _measurement_operator(U, "Chiral_condensate_measurement", fermiontype, mass, κ, r, L5, M, eps_CG, MaxCGstep, BoundaryCondition, kappa)
+        self.Nr = int(Nr)
+        self.factor = Nf / 4.0 if fermiontype == "Staggered" else 1.0
+        self.randomseed = int(randomseed)
+        lat = U.lattice
+        self._temps = [Fermionfields(lat, self.D.kind) for _ in range(3)]
+
+    def measure(self, U):
+        p, r, t = self._temps
+        D = self.D(U)
+        pbp = 0.0 + 0.0j
+        for ir in range(self.Nr):
+            clear_fermion_(p)
+            Z4_distribution_fermi_(r, self.randomseed + ir)
+            if D.kind == STAGGERED:
+                clear_fermion_(t)
+                solve_DinvX_(t, DdagD_operator(D), r)
+                mul_(p, D.adjoint(), t)
+            else:
+                solve_DinvX_(p, D, r)
+            pbp += dot(r, p)
+        NV = float(np.prod(U.lattice.L))
+        return (pbp / self.Nr).real / NV * self.factor
 
 
 # ------------------------------------------------------------------------------------ pseudofermion action and force
