@@ -99,11 +99,15 @@ int lqcd_ctx_sync(lqcd_ctx_t ctx);
  * two buffers -- 9 instead of 10 spinor passes per iteration on average, identical iterates; K = 3..8 (round 5): a ring of K search-direction buffers,
  * x += K terms every K-th iteration, (4 K + 1) / K update passes per iteration; 1 [default]: 2 on an unpartitioned lattice, 8 on a partitioned one (what was measured
  * faster in each case); 0: x every iteration; under cg_fused = 3 it has no meaning where the residual ring applies),
- * cg_rring (cg_fused = 3; K = 4 [default], 2 or 8, 0: off, other values are refused: the fp64 Wilson D^+D CG -- r = 1, no clover term, one unpartitioned GPU without a
+ * cg_rring (cg_fused = 3; K = 8 [default], 2 or 4, 0: off, other values are refused: the fp64 Wilson D^+D CG -- r = 1, no clover term, one unpartitioned GPU without a
  * communicator, scalar-addressing kernel, beyond cg_small -- forms D p by the recurrence D p' = D r' + beta D p from the residual D^+ has just written, keeps the K
  * residuals of a batch in a ring and brings p and x up to date once per K iterations in one streaming launch; the recurrence restarts from an exact D p there.  2064 instead of
- * 2400 bytes per site and iteration at K = 4, K - 2 more work vectors; the iterates equal those of cg_fused = 2 to rounding; everything else runs as cg_fused = 2.
+ * 2400 bytes per site and iteration at K = 4 (1992 at K = 8), K - 2 more work vectors; the iterates equal those of cg_fused = 2 to rounding; everything else runs as cg_fused = 2.
  * Read-only cg_rring_active: the K in use by the last CG set-up, 0 if the form did not apply),
+ * cg_sweep_alt (1 [default]: in a Wilson CG that runs in temporal gauge every D^+ launch walks the (pass, t) slabs of the XCD tile sweep backwards, so that each stencil launch
+ * begins on the slabs the launch before it touched last; identical bits; 0: every launch forwards.  Read-only cg_sweep_alt_active: does the last CG set-up reverse its D^+),
+ * dslash_sweep (measurement and tests; 1: every plain full-lattice application -- mul!, lqcd_bench_dslash -- that takes an eligible instance of the scalar-addressing kernel
+ * walks its slabs backwards; read-only sweep_rev_active: did the last such launch),
  * halo_fold (1 [default], round 5: where the collective timing picks the one-stream halo schedule 3, the stencil launch takes the boundary hops from the ghost
  * buffers itself -- no exterior kernel, for every operator and both precisions; read-only halo_fold_active), cg_persist (1 [default]: a staggered CG on an unpartitioned lattice of
  * at most 256 chunks of 64 sites runs as ONE launch -- initial residual and all iterations, two grid-wide synchronisations per iteration, every wait bounded: if the workgroups are not all resident (a busy GPU) x is left untouched, the solve is

@@ -426,6 +426,7 @@ int op_apply_async(lqcd_op_s* op, lqcd_spinor_s* out, lqcd_spinor_s* in, int dag
     s.gauge12t = gauge12t;      // the CG in temporal gauge: `in` and `out` are rotated vectors
     s.norm_partial = norm_partial;
     s.skip_flag = skip_flag;
+    s.sweep_rev = op->ctx->tun.dslash_sweep != 0;      // (measurement and tests: off by default)
     return stencil_apply(op->ctx, s);
 }
 

@@ -336,6 +336,10 @@ static int* param_ptr(lqcd_ctx_s* c, const char* key) {
     if (!strcmp(key, "cg_small")) return &c->tun.cg_small;
     if (!strcmp(key, "cg_tgauge")) return &c->tun.cg_tgauge;
     if (!strcmp(key, "tgauge_active")) return &c->tun.tgauge_active;
+    if (!strcmp(key, "cg_sweep_alt")) return &c->tun.cg_sweep_alt;
+    if (!strcmp(key, "cg_sweep_alt_active")) return &c->tun.cg_sweep_alt_active;
+    if (!strcmp(key, "dslash_sweep")) return &c->tun.dslash_sweep;
+    if (!strcmp(key, "sweep_rev_active")) return &c->tun.sweep_rev_active;
     if (!strcmp(key, "cg_persist")) return &c->tun.cg_persist;
     if (!strcmp(key, "md_remap")) return &c->tun.md_remap;
     if (!strcmp(key, "staple_recon")) return &c->tun.staple_recon;

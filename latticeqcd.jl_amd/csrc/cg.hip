@@ -521,6 +521,7 @@ static int cg_enqueue_rring(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
     StencilCall s2;
     LQCHK(make_full_call(op, rn, w.tmp, 1, s2));
     s2.gauge12t = gt;
+    s2.sweep_rev = w.sweep_alt ? 1 : 0;      // D^+ backwards: it starts on the slabs the D above wrote last, the next D starts on the slabs it writes last
     s2.norm_partial = c->d_partial;
     s2.upd_scal = c->d_scal;
     for (int q = 0; q < 2; q++) { s2.upd[q] = spinor_block(rn, q); s2.upd_src[q] = spinor_block(rk, q); }
@@ -657,6 +658,7 @@ static int cg_iter_fused(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
     StencilCall s2;
     LQCHK(make_full_call(op, po, w.tmp, 1, s2));          // update mode writes r only: `out` is a placeholder (the buffer that is dead until the p update)
     s2.gauge12t = gt;
+    s2.sweep_rev = w.sweep_alt ? 1 : 0;      // (see cg_enqueue_rring)
     s2.norm_partial = c->d_partial;
     if (fold) s2.scal_w = c->d_scal;
     s2.upd_scal = c->d_scal;
@@ -762,6 +764,10 @@ int cg_setup(lqcd_op_s* op, lqcd_spinor_s* x, lqcd_spinor_s* b, CgWork& w, doubl
     w.form = cg_choose_form(op, w);
     w.rring = w.form == CgForm::RRing ? c->tun.cg_rring : 0;
     c->tun.cg_rring_active = w.rring;
+    // the alternating sweep: the forms whose D^+ is a launch of the temporal-gauge instance (away from the seam it loads no time-like link, so no streaming hint sits on the
+    // first use of one when t runs backwards).  Fixed here like the form: no iteration reads the tunable.
+    w.sweep_alt = c->tun.cg_sweep_alt != 0 && w.tgauge && (w.form == CgForm::RRing || w.form == CgForm::Fused || w.form == CgForm::DeferX);
+    c->tun.cg_sweep_alt_active = w.sweep_alt ? 1 : 0;
     w.ring = 2;
     if (w.form == CgForm::DeferX) {      // the ring of search-direction buffers (cg_defer_x = K): K - 2 more vectors, or the two-buffer form if the pool cannot grow
         int want = cg_ring_wanted(op);

@@ -473,7 +473,7 @@ struct Tunables {
     int nt_store = 1;         // output spinor stored non-temporally (it is not read again by this kernel: keeps its lines out of the L2) -1..3 %
     int cg_fused = 3;         // 0: reference form (c1 = p.q), 1: |Dp|^2 from the stencil, 2: + r-update fused into D^+, x/p updates merged, 3 (default): 2 +, where
                               // the scalar-addressing Wilson kernel runs on one unpartitioned GPU, D p by recurrence from D r and p, x updated once per cg_rring iterations
-    int cg_rring = 4;         // cg_fused = 3: K = 2, 4 or 8 residual slots (p and x are brought up to date every K-th iteration; K divides the 8 iterations of a captured burst); 0: form off
+    int cg_rring = 8;         // cg_fused = 3: K = 2, 4 or 8 (default) residual slots (p and x are brought up to date every K-th iteration; K divides the 8 iterations of a captured burst); 0: form off
     int cg_rring_active = 0;  // read-only: the K in use by the last CG set up through cg_setup, 0 if the form did not apply
     int graph = 0;            // capture solver iterations in a hipGraph
     int persist_per_cu = 2;   // variant 3: resident workgroups per CU
@@ -537,6 +537,14 @@ struct Tunables {
                               // its stencils skip the time-like links below the seam.  0: off; 1 (default): beyond the cg_small regime (more than 1024 stencil workgroups);
                               // 2: whenever admissible (tests)
     int tgauge_active = 0;    // read-only: 1 if the last CG set up through cg_setup ran in temporal gauge
+    int cg_sweep_alt = 1;     // Wilson CG in temporal gauge (residual ring, Fused and DeferX forms): every D^+ launch of an iteration walks the (pass, t) slabs of the XCD tile
+                              // sweep backwards (StencilCall::sweep_rev), so that it begins where the D before it ended and the D behind it begins where it ends -- the
+                              // neighbour, link and centre streams of the first slabs of a launch are then what the launch before touched last.  Same sites, same
+                              // operations per workgroup: identical bits.  0: every launch forwards
+    int cg_sweep_alt_active = 0;   // read-only: 1 if the last CG set up through cg_setup reverses its D^+ launches
+    int dslash_sweep = 0;     // measurement and tests: 1 reverses the sweep of every plain full-lattice application (op_apply_async: mul!, lqcd_bench_dslash) that takes
+                              // an eligible instance of the scalar-addressing kernel
+    int sweep_rev_active = 0; // read-only: 1 if the last launch of the scalar-addressing kernel walked its slabs backwards
     int cg_skip_done = 1;     // fused CG: the first Dslash of an iteration checks the convergence flag as well (0: only the second does)
     int clover_transport = 0; // 1: build the clover sums by the plaquette-transport passes also on an unpartitioned lattice (tests)
     int stag_both = 0;            // 1: staggered split kernel issues the loads of both hops of a direction back to back (unpartitioned lattices)
@@ -1017,6 +1025,8 @@ struct StencilCall {
     // s = v + beta s_old in place, beta = upd_scal[S_BETA]; |s|^2 partials; the plain launch's store policy; a no-op once upd_scal[S_DONE] is set.
     const double2* upd_src[2] = {nullptr, nullptr};
     int upd_rec = 0;
+    int sweep_rev = 0;            // 1: the launch walks the (pass, t) slabs of the XCD tile sweep backwards, order inside a slab kept (stencil.hip dirsplit_s_block).  Honoured by the
+                                  // plain, update-mode and temporal-gauge instances of the scalar-addressing kernel with one workgroup per chunk; every other launch ignores it
     const double* skip_flag = nullptr;  // device scalar block: the interior launch is a no-op once skip_flag[S_DONE] is set (iterations
                                         // enqueued behind the converging one in a burst)
     // small lattices (cg_small): no separate reduction launches.  The update-mode kernel sums the <= 1024 block partials of the previous

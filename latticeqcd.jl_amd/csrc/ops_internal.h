@@ -42,6 +42,8 @@ struct CgWork {
     const double2* links_t = nullptr;      // lqcd_gauge_s::data12t of the field version the solve was set up on
     const double2* gfix = nullptr;
     uint64_t gauge_version = 0;
+    // alternating sweep (decided once in cg_setup from the tunable cg_sweep_alt, temporal gauge only): every D^+ launch of an iteration sets StencilCall::sweep_rev
+    bool sweep_alt = false;
 };
 int cg_work_get(lqcd_ctx_s* c, int kind, CgWork& w);      // the four work vectors of a solve from the context's scratch pool (the ring's extra buffers follow in cg_setup)
 void cg_work_put(CgWork& w);

@@ -375,6 +375,10 @@ struct PipeArgs {
     double* scal_w;
     real a, b;
     int nt_store;
+    // scalar-addressing kernel, one workgroup per chunk (plain, update-mode and temporal-gauge instances): the slab of a workgroup is (pass, t) of the map below -- what the
+    // eight XCDs work on at the same time -- numbered pass * LT + t in dispatch order.  sweep_rev: workgroup b runs the virtual block of slab nslab - 1 - q with its XCD, parity
+    // and place inside the slab kept (StencilCall::sweep_rev)
+    int sweep_rev, nslab;
     int nvirt, both, pmode;
     int XH, L1, L2, LT, nch;
     FastDiv dXH;
@@ -1095,6 +1099,19 @@ __device__ __forceinline__ void dirsplit_s_block(const PipeArgs& a, real2 (*part
             if ((a.fsel == 1) == bnd) return;
         }
     }
+    // Reversed sweep (PipeArgs::sweep_rev), on the scalar unit: only pass and t are mirrored.  The order inside a slab stays -- the streaming
+    // hint on the backward use of a link (NTB) assumes that use is the later one, and mirroring z or y would put it on the first (LABNOTES: 0.60 against 0.41 ms).  Everything
+    // downstream -- pipe_site, the partial index -- runs on the virtual block; the done-flag tests above stay keyed on blockIdx.x.
+    if constexpr (!DOT && !DELTA && !DW5 && !FOLD && !CINV) {
+        if (a.sweep_rev) {
+            int j = vb >> 3;
+            const int pb = a.both ? (j & 1) : 0;
+            j = a.both ? (j >> 1) : j;
+            const int q = fdiv_nb(j, a.d_cpr);       // this workgroup's slab in dispatch order
+            j += (a.nslab - 1 - 2 * q) * a.cpr;      // slab nslab - 1 - q, same place inside it
+            vb = ((a.both ? 2 * j + pb : j) << 3) | (vb & 7);
+        }
+    }
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     real nrm = 0.0, dre = 0.0, dim = 0.0, dre2 = 0.0, dim2 = 0.0;
@@ -1780,6 +1797,7 @@ static PipeArgs make_pipe_args(lqcd_ctx_s* c, const KArgs& k, const StencilCall&
     a.norm_partial = k.norm_partial; a.upd_scal = k.upd_scal; a.skip = k.skip; a.scal_w = k.scal_w;
     a.a = k.a; a.b = k.b;
     a.nt_store = (k.nt & 4) != 0;
+    a.sweep_rev = 0; a.nslab = 0;      // (set by the one launch site that honours StencilCall::sweep_rev)
     a.nvirt = k.nblocks; a.both = s.parity_mode == 2; a.pmode = s.parity_mode == 2 ? 0 : s.parity_mode;
     a.XH = k.g.XH; a.L1 = k.g.L[1]; a.L2 = k.g.L[2]; a.LT = k.g.L[3]; a.nch = k.g.nch; a.dXH = k.g.dXH;
     for (int mu = 0; mu < 4; mu++) {
@@ -1803,6 +1821,19 @@ static PipeArgs make_pipe_args(lqcd_ctx_s* c, const KArgs& k, const StencilCall&
         if (s.fold && k.g.part[mu]) a.fold |= 1 << mu;
     }
     return a;
+}
+
+// The reversed sweep (StencilCall::sweep_rev) of the scalar-addressing kernel with one workgroup per chunk: the slabs of the launch.  Honoured by the plain, update-mode
+// and temporal-gauge instances only (dslash_pipe = 2; not the five-dimensional, folded and 12 + delta launches).
+static void pipe_sweep_args(lqcd_ctx_s* c, const KArgs& k, const StencilCall& s, bool delta, PipeArgs& a) {
+    const int par = s.parity_mode == 2 ? 2 : 1;
+    const bool plain = c->tun.dslash_pipe == 2 && s.dw_ls <= 1 && !s.fold && !delta;
+    const bool map_ok = k.cps > 0 && k.cpr > 0 && k.nblocks % (8 * par * k.cpr) == 0 && k.nblocks / (8 * par * k.cpr) == (k.nsub / 8) * k.g.L[3];
+    a.nslab = map_ok ? k.nblocks / (8 * par * k.cpr) : 0;
+    a.sweep_rev = 0;
+    if (!plain || !map_ok) return;
+    a.sweep_rev = s.sweep_rev ? 1 : 0;
+    c->tun.sweep_rev_active = a.sweep_rev;
 }
 
 static HArgs make_hargs(lqcd_ctx_s* c, const StencilCall& s);
@@ -1998,6 +2029,7 @@ int launch_stencil_interior(lqcd_ctx_s* c, const StencilCall& s) {
             if (c->tun.dslash_pipe == 3) { a.ctr = nullptr; a.per_wg = wilson_pipe_per_wg(c, k.nblocks); }
             const dim3 pg(c->tun.dslash_pipe == 1 ? wilson_pipe_grid(c, k.nblocks, s.prec) : c->tun.dslash_pipe == 3 ? k.nblocks / a.per_wg : k.nblocks), pb(256);
             const bool ntb = (k.nt & 1) != 0;
+            pipe_sweep_args(c, k, s, delta, a);      // (read by the launches of the last branch below only)
 #ifndef LQCD_F32
             if (s.dw_ls > 1) {      // Domainwall: the L5 slices in one launch, fifth-direction hops in the epilogue (plain loads for the backward link: it is re-used by the next slice)
                 if (c->tun.dslash_pipe != 2 || delta) { set_error("stencil: the five-dimensional launch needs the scalar-addressing kernel in its plain mode"); return LQCD_ERR_UNSUPPORTED; }
