@@ -134,7 +134,9 @@ int lqcd_ctx_sync(lqcd_ctx_t ctx);
  * equations as two even-odd BiCGStab solves under the reference's stopping rule; 0: CG), bicg_mixed (1: lqcd_solve_bicgstab_eo on the plain Wilson operator runs an fp32 inner
  * chain inside an fp64 defect correction, the stopping rule holds for the true fp64 residual; mixed_action_solver = 1 switches it on for the action solves), lazy_links (1: the per-direction link-call triples are recorded and fused -- the temporaries of a completed triple are then never written, so the C ABI's default is 0 (eager) and the Julia / Python bindings switch it on when they create a context,
  * see lqcd_link_*; read-only lazy_open, lazy_deferred), lazy_merge (1 [default]: a complete link update U <- exp(a P) U waits unlaunched and a second one of the same
- * fields, with nothing in between that reads U or writes P, adds its step -- the back-to-back half steps of runMD_QPQ_sw!, standardMD.jl:146-166).
+ * fields, with nothing in between that reads U or writes P, adds its step -- the back-to-back half steps of runMD_QPQ_sw!, standardMD.jl:146-166);
+ * several right-hand sides: mrhs_active (read-only: columns per stencil launch of the last lqcd_*_multi call, 0 if it looped over the single-column entries), meson_mrhs (1: the meson
+ * entries solve the four spin columns of a source colour with one lqcd_solve_bicgstab_eo_multi call; 0 [default]: twelve single solves).
  * Threads: calls on one context must not overlap (one lock per context in a host that uses several threads).  The exception is lqcd_gauge_destroy / lqcd_spinor_destroy,
  * which garbage collectors call from finalizer threads: with lazy_links on, a gauge-shaped field destroyed from another thread than the context's own (the creating thread,
  * or the one that last set adopt_thread = 1) is parked and freed by the context's thread at its next lqcd_gauge_create / lqcd_ctx_sync / lqcd_ctx_destroy (read-only
@@ -464,6 +466,30 @@ int lqcd_meson_contract(const lqcd_spinor_t* cols, int ncol, double* table /* [1
 int lqcd_meson_correlators(lqcd_op_t op, const int src[4], double eps, int maxiter, double* table /* [16][gLt] */, int* iters /* [12] or NULL */);
 /* the reference's Pion_correlator: Wilson/clover = row 15 of the above; staggered = 3 colour solves (CG on D^+D, then D^+), C(t) = sum |G|^2 */
 int lqcd_pion_correlator(lqcd_op_t op, const int src[4], double eps, int maxiter, double* C /* [gLt] */, int* iters /* [12] or [3] or NULL */);
+
+/* ---------------------------------------------------------------- several right-hand sides (csrc/stencil_mrhs.hip, csrc/bicgstab_eo_mrhs.hip)
+ * The operator applied to n columns that share the gauge field: one launch of the multi-column direction-split kernel loads the links once for up to four columns
+ * (a call with more columns runs ceil(n / 4) launches), and the even-odd BiCGStab batched over the columns -- the recurrences and the stopping rule of
+ * lqcd_solve_bicgstab_eo (half-step exit on |s|^2 < eps, then |r|^2 < eps, absolute) per column, every column with its own Krylov scalars, iteration count and done
+ * flag: a converged column is frozen while the others go on.
+ * Contracts: 1 <= n <= LQCD_MRHS_MAX; every column obeys the contract of the single-column entry (lqcd_op_hop: out / in opposite parity subsets, the same for every
+ * column; lqcd_op_apply, lqcd_solve_bicgstab_eo: FULL fields, x holds the initial guess); all fields belong to the operator's context; output columns are pairwise
+ * distinct; input columns may repeat; inputs are never written (an output that is also an input of any column is refused).
+ * Refusals, outputs untouched: LQCD_ERR_ARG for null pointers, n out of range, a wrong subset or kind, mixed contexts, duplicate outputs; LQCD_ERR_UNSUPPORTED
+ * (lqcd_last_error names the case) for a staggered or Domainwall operator and for an in-process PE grid.
+ * The multi-column kernel runs for the Wilson operator with r = 1, no clover term, on one unpartitioned GPU without a communicator, Vh % 64 == 0 (12-real links while the
+ * field passes the gate of gauge_recon, all 18 reals otherwise).  Anything else -- r != 1, Wilson-clover, a partitioned lattice or a communicator, Vh % 64 != 0 -- loops
+ * over the single-column entries: the results are then those entries' bits.  Read-only key mrhs_active: columns per stencil launch of the last multi call, 0 if it fell back.
+ * Key meson_mrhs (default 0): 1 = lqcd_meson_correlators and the Wilson branch of lqcd_pion_correlator solve the four spin columns of a source colour with one
+ * lqcd_solve_bicgstab_eo_multi call (four point sources resident instead of one; the contraction is unchanged); 0 = nothing about those entries changes.
+ * lqcd_solve_bicgstab_eo_multi returns LQCD_OK when every column converged, otherwise LQCD_ERR_NOT_CONVERGED with iters / final_rr filled per column and every x a
+ * finite best effort (the odd halves are written on non-convergence too).  Reductions have a fixed order: two calls give the same bits, and a column's result does not
+ * depend on its slot. */
+#define LQCD_MRHS_MAX 12
+int lqcd_op_hop_multi(lqcd_op_t op, int n, const lqcd_spinor_t* out, const lqcd_spinor_t* in, int dagger);   /* n x lqcd_op_hop */
+int lqcd_op_apply_multi(lqcd_op_t op, int n, const lqcd_spinor_t* out, const lqcd_spinor_t* in, int dagger); /* n x lqcd_op_apply, FULL fields */
+int lqcd_solve_bicgstab_eo_multi(lqcd_op_t op, int n, const lqcd_spinor_t* x, const lqcd_spinor_t* b, int dagger,
+                                 double eps, int maxiter, int* iters /* [n] or NULL */, double* final_rr /* [n] or NULL */);
 
 /* ---------------------------------------------------------------- quenched heatbath and overrelaxation (src/updates/heatbath.jl:1-44)
  * Plaquette action S_g = -(beta/3) sum_plaq Re tr U_p.  One heatbath sweep: mu = 0..3, even then odd sites, every link of that parity in place by

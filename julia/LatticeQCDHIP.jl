@@ -40,7 +40,8 @@ import LatticeDiracOperators: Dirac_operator, DdagD_operator, FermiAction, Initi
 
 export Initialize_HIPGaugefields, HIPLattice, HIPLink, HIPTALink, HIPFermion, HIPDirac, HIPFermiAction, reunitarize!, activate!, deactivate!,
     HIPGradientflow, flow_observables, energy_density, topological_charge, gradient_flow_measure, HIPHeatbath, heatbath_measure,
-    wilson_loops, calc_Wilson_loop, meson_correlators, pion_correlator, Pion_correlator_measurement, measure
+    wilson_loops, calc_Wilson_loop, meson_correlators, pion_correlator, Pion_correlator_measurement, measure,
+    hop_multi!, mul_multi!, solve_DinvX_multi!
 
 const LIB = get(ENV, "LQCD_HIP_LIB", joinpath(@__DIR__, "..", "latticeqcd.jl_amd", "csrc", "liblqcd_hip.so"))
 
@@ -586,6 +587,30 @@ function solve_DinvX!(y::HIPFermion, D::HIPDirac, x::HIPFermion)
         check(ccall((:lqcd_solve_bicgstab, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Float64, Cint, Ref{Cint}, Ref{Float64}),
                     D.h, y.h, x.h, D.dagger, D.eps_CG, D.MaxCGstep, it, rr))
     end
+end
+
+# several right-hand sides (include/lqcd_hip.h "several right-hand sides"): up to 12 columns share the links of one launch.  The context key meson_mrhs
+# switches meson_correlators / pion_correlator to the batched solver; nothing changes here
+function hop_multi!(ys::Vector{HIPFermion}, D::HIPDirac, xs::Vector{HIPFermion})
+    length(ys) == length(xs) || error("hop_multi!: as many output as input columns")
+    check(ccall((:lqcd_op_hop_multi, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Cint),
+                D.h, length(ys), [y.h for y in ys], [x.h for x in xs], D.dagger))
+    ys
+end
+function mul_multi!(ys::Vector{HIPFermion}, D::HIPDirac, xs::Vector{HIPFermion})
+    length(ys) == length(xs) || error("mul_multi!: as many output as input columns")
+    check(ccall((:lqcd_op_apply_multi, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Cint),
+                D.h, length(ys), [y.h for y in ys], [x.h for x in xs], D.dagger))
+    ys
+end
+# solve_DinvX!(ys[j], D, xs[j]) for every column with the batched even-odd BiCGStab; returns the per-column iteration counts and residuals
+function solve_DinvX_multi!(ys::Vector{HIPFermion}, D::HIPDirac, xs::Vector{HIPFermion})
+    length(ys) == length(xs) || error("solve_DinvX_multi!: as many solution as source columns")
+    D.method_CG == "bicgstab_evenodd" || error("solve_DinvX_multi!: method_CG = $(D.method_CG) is not supported (bicgstab_evenodd)")
+    its, rrs = zeros(Cint, length(ys)), zeros(Float64, length(ys))
+    check(ccall((:lqcd_solve_bicgstab_eo_multi, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Cint, Float64, Cint, Ptr{Cint}, Ptr{Float64}),
+                D.h, length(ys), [y.h for y in ys], [x.h for x in xs], D.dagger, D.eps_CG, D.MaxCGstep, its, rrs))
+    Int.(its), rrs
 end
 
 # shiftedcg(vec_x, vec_β, x, A, b): the RHMC solver (README.md:132)

@@ -285,6 +285,7 @@ extern "C" int lqcd_ctx_destroy(lqcd_ctx_t c) {
     (void)hipFree(c->hb_tab);
     (void)hipFree(c->wl_s); (void)hipFree(c->wl_partial); (void)hipFree(c->wl_tab);
     (void)hipFree(c->ms_partial); (void)hipFree(c->ms_tab);
+    (void)hipFree(c->mrhs_block);
     (void)hipFree(c->clover_ext); (void)hipFree(c->clover_ext_buf[0]); (void)hipFree(c->clover_ext_buf[1]);
     if (c->has_comm && !c->peer.on) { ncclCommDestroy(c->comm); ncclCommDestroy(c->comm_red); }
     comm_teardown(c);      // the peer-mapped backend's windows (comm.hip)
@@ -385,6 +386,8 @@ static int* param_ptr(lqcd_ctx_s* c, const char* key) {
     if (!strcmp(key, "bicg_mixed")) return &c->tun.bicg_mixed;
     if (!strcmp(key, "action_eo_solver")) return &c->tun.action_eo_solver;
     if (!strcmp(key, "bicg_xrp_active")) return &c->tun.bicg_xrp_active;
+    if (!strcmp(key, "mrhs_active")) return &c->tun.mrhs_active;
+    if (!strcmp(key, "meson_mrhs")) return &c->tun.meson_mrhs;
     if (!strcmp(key, "peer_timeout_ms")) return &c->peer.timeout_ms;
     return nullptr;
 }

@@ -614,6 +614,9 @@ struct Tunables {
                               // inside an fp64 defect correction; the stopping rule holds for the true fp64 residual.  mixed_action_solver = 1 switches it on for the action solves
     int dslash_s18 = 1;       // dslash_pipe = 2: the scalar-addressing kernel also for the 18 stored reals (round 4: its instance no longer spills at 3 waves per SIMD --
                               // the diagonal term and the old r of the update mode are requested behind the hops); 0: the plain direction-split kernel there
+    int mrhs_active = 0;      // read-only: columns per stencil launch of the last lqcd_*_multi call (stencil_mrhs.hip), 0 if it looped over the single-column entries
+    int meson_mrhs = 0;       // 1: lqcd_meson_correlators / the Wilson branch of lqcd_pion_correlator solve the four spin columns of a source colour with ONE
+                              // lqcd_solve_bicgstab_eo_multi call (four point sources resident instead of one); the contraction is unchanged.  0 (default): twelve single solves
     int gauge_delta = 1;      // fields that fail the 12-real gate but lie within 1e-9 of the group (reference-format configurations) take the "12 + delta" links in the
                               // scalar-addressing Wilson kernel: 896 B/site moved instead of 960, results equal to the 18-real kernel's to fp64 rounding; 0: always 18 reals
 };
@@ -844,6 +847,8 @@ struct lqcd_ctx_s {
     size_t ms_partial_n = 0;
     double* ms_tab = nullptr;           // ... device table [16][gLt] of the time-slice sums
     size_t ms_tab_n = 0;
+    double* mrhs_block = nullptr;       // several right-hand sides (bicgstab_eo_mrhs.hip): per-column Krylov scalars + done flags [n][B_END - B_RHO], then the columns' partial sums
+    size_t mrhs_block_n = 0;
     double2* clover_q[2] = {};          // clover sums / transport ping-pong, six 3x3 matrices per site (clover.hip)
     double2* clover_ext = nullptr;      // halo-extended links + Lambda matrices of the partitioned clover force, and its face buffers
     size_t clover_ext_bytes = 0;
@@ -939,6 +944,7 @@ struct lqcd_op_s {
     uint64_t clover_inv_version = 0;
     double2* clover_lambda = nullptr;   // six Hermitian 3x3 matrices per site: scratch of the clover force
     int bicg32_hint[2][4] = {};         // mixed-precision chain: iterations the last solve's correction steps took, per step, for D and D^+ apart (the action solves alternate) (mixed.hip)
+    int bicg_mrhs_hint = 0;             // the largest per-column count of the last lqcd_solve_bicgstab_eo_multi with this operator (its polling schedule)
     int bicg_hint = 0;                  // iterations the last even-odd BiCGStab solve with this operator took (polling schedule of the next one)
     // LQCD_DOMAINWALL (domainwall.hip): km = the fermion mass m; the 4-D Wilson operator of the slices (hop coefficient 1/2), five-dimensional work fields
     int L5 = 0;

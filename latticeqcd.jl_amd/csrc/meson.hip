@@ -258,13 +258,28 @@ static int ms_wilson_correlators(lqcd_op_s* op, const int src[4], double eps, in
     lqcd_spinor_s* x[4];
     for (int is = 0; is < 4; is++) x[is] = pool.get(LQCD_WILSON, LQCD_FULL);
     if (!(b && x[0] && x[1] && x[2] && x[3])) { set_error("lqcd_meson_correlators: out of device memory"); return LQCD_ERR_HIP; }
+    // tunable meson_mrhs = 1: the four spin columns of a source colour as ONE multi-column solve (four point sources resident instead of one); the contraction is unchanged
+    const bool multi = c->tun.meson_mrhs != 0;
+    lqcd_spinor_s* bm[4] = {b, nullptr, nullptr, nullptr};
+    if (multi) {
+        for (int is = 1; is < 4; is++) bm[is] = pool.get(LQCD_WILSON, LQCD_FULL);
+        if (!(bm[1] && bm[2] && bm[3])) { set_error("lqcd_meson_correlators: out of device memory"); return LQCD_ERR_HIP; }
+    }
     LQCHK(ms_begin(c, MS_NCHAN));
     int its[12];
     for (int ic = 0; ic < 3; ic++) {
-        for (int is = 0; is < 4; is++) {
-            LQCHK(lqcd_spinor_point_source(b, src, ic, is));
-            LQCHK(lqcd_spinor_zero(x[is]));
-            LQCHK(lqcd_solve_bicgstab_eo(op, x[is], b, 0, eps, maxiter, &its[4 * ic + is], nullptr));
+        if (multi) {
+            for (int is = 0; is < 4; is++) {
+                LQCHK(lqcd_spinor_point_source(bm[is], src, ic, is));
+                LQCHK(lqcd_spinor_zero(x[is]));
+            }
+            LQCHK(lqcd_solve_bicgstab_eo_multi(op, 4, x, bm, 0, eps, maxiter, &its[4 * ic], nullptr));
+        } else {
+            for (int is = 0; is < 4; is++) {
+                LQCHK(lqcd_spinor_point_source(b, src, ic, is));
+                LQCHK(lqcd_spinor_zero(x[is]));
+                LQCHK(lqcd_solve_bicgstab_eo(op, x[is], b, 0, eps, maxiter, &its[4 * ic + is], nullptr));
+            }
         }
         LQCHK(ms_add_block(c, x));
     }

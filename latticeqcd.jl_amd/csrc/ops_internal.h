@@ -143,6 +143,24 @@ int bicgstab_eo_wilson(lqcd_op_s* op, lqcd_spinor_s& xe, lqcd_spinor_s* rhs, lqc
 int bicgstab_eo_wilson_mixed(lqcd_op_s* op, lqcd_spinor_s& xe, lqcd_spinor_s* rhs, lqcd_spinor_s* const w[6], lqcd_spinor_s* to, int dg, double eps,
                              int maxiter, int* iters, double* final_rr, const double2* Ai = nullptr);
 
+// stencil_mrhs.hip: the direction-split parity hop on several columns that share the links, out_j = a xin_j + b H in_j (Wilson r = 1, fp64, one unpartitioned GPU)
+struct MrhsCall {
+    int n = 0;                    // columns, 1 .. LQCD_MRHS_MAX: ceil(n / 4) launches
+    int parity_mode = 0;          // 0 even out, 1 odd out, 2 both (FULL fields)
+    int dagger = 0;
+    double a = 0.0, b = 1.0;
+    double2* out[2][LQCD_MRHS_MAX] = {};          // per parity block, like StencilCall
+    const double2* in[2][LQCD_MRHS_MAX] = {};
+    const double2* xin[2][LQCD_MRHS_MAX] = {};    // may be null when a == 0
+    // dot epilogue (parity_mode 0 / 1): per column and workgroup Re / Im <z_j, out_j> (dot_conj: <out_j, z_j>) and |out_j|^2 -> dot_partial[j][3 workgroup + (0, 1, 2)]
+    const double2* dot_z[LQCD_MRHS_MAX] = {};
+    double* dot_partial[LQCD_MRHS_MAX] = {};
+    int dot_conj = 0;
+    const double* done[LQCD_MRHS_MAX] = {};       // a column whose word is non-zero is skipped (no loads, no stores); the word is written by no kernel of the launch
+};
+bool mrhs_applies(lqcd_op_s* op);                 // the multi-column kernel runs for this operator; otherwise the callers loop over the single-column entries
+int mrhs_hop_launch(lqcd_op_s* op, const MrhsCall& m);
+
 // domainwall.hip: the five-dimensional operator behind the entry points of the four-dimensional ones
 int dw_op_apply(lqcd_op_s* op, lqcd_spinor_s* out, lqcd_spinor_s* in, int dagger);
 int dw_op_apply_DdagD(lqcd_op_s* op, lqcd_spinor_s* out, lqcd_spinor_s* in);

@@ -704,6 +704,48 @@ def hop_(y, D, x):
     return y
 
 
+# several right-hand sides (include/lqcd_hip.h "several right-hand sides"; csrc/stencil_mrhs.hip, csrc/bicgstab_eo_mrhs.hip)
+MRHS_MAX = 12
+
+
+def _multi(ys, xs):
+    ys, xs = list(ys), list(xs)
+    if not ys or len(ys) != len(xs):
+        raise LQCDError(_l.ERR_ARG, "multi-column call: need as many output as input columns, at least one")
+    return len(ys), (C.c_void_p * len(ys))(*[y._h for y in ys]), (C.c_void_p * len(xs))(*[x._h for x in xs])
+
+
+def hop_multi_(ys, D, xs):
+    """ys[j] (EVEN|ODD) = H xs[j] (opposite parity) for up to 12 columns that share the links (lqcd_op_hop_multi)."""
+    n, out, inp = _multi(ys, xs)
+    check(_l.lib().lqcd_op_hop_multi(D._h, n, out, inp, int(D.dagger)))
+    return ys
+
+
+def mul_multi_(ys, A, xs):
+    """mul!(ys[j], A, xs[j]) for A = D or D' on up to 12 FULL columns (lqcd_op_apply_multi)."""
+    n, out, inp = _multi(ys, xs)
+    check(_l.lib().lqcd_op_apply_multi(A._h, n, out, inp, int(A.dagger)))
+    return ys
+
+
+def solve_DinvX_multi_(ys, A, xs, return_info=False):
+    """solve_DinvX!(ys[j], A, xs[j]) for every column with the batched even-odd BiCGStab (lqcd_solve_bicgstab_eo_multi; method_CG = "bicgstab_evenodd"):
+    ys hold the initial guesses, the stopping rule real(r.r) < eps_CG holds per column.  return_info -> ([iterations], [residuals]).  A column that does not
+    converge within MaxCGstep raises NotConverged with the per-column lists in .iters / .final_rr; every ys[j] is then a finite best effort."""
+    if A.method_CG not in ("bicgstab_evenodd", "preconditiond_bicgstab"):
+        raise LQCDError(_l.ERR_ARG, f"solve_DinvX_multi_: method_CG = {A.method_CG} is not supported (bicgstab_evenodd)")
+    n, out, inp = _multi(ys, xs)
+    its, rrs = (C.c_int * n)(), (C.c_double * n)()
+    st = _l.lib().lqcd_solve_bicgstab_eo_multi(A._h, n, out, inp, int(A.dagger), C.c_double(A.eps_CG), int(A.MaxCGstep), its, rrs)
+    try:
+        check(st)
+    except NotConverged as e:
+        e.iters, e.final_rr = list(its), list(rrs)
+        raise
+    return (list(its), list(rrs)) if return_info else None
+
+
 def solve_DinvX_(y, A, x, return_info=False):
     """solve_DinvX!(y, A, x): y = A^{-1} x.  A::DdagD_operator -> CG; A::Dirac_operator -> BiCGStab
     ("bicgstab"), its even-odd preconditioned form ("bicgstab_evenodd") or BiCG ("bicg", the reference's default).  Stopping rule real(r.r) < eps_CG;
