@@ -108,6 +108,11 @@ int lqcd_ctx_sync(lqcd_ctx_t ctx);
  * begins on the slabs the launch before it touched last; identical bits; 0: every launch forwards.  Read-only cg_sweep_alt_active: does the last CG set-up reverse its D^+),
  * dslash_sweep (measurement and tests; 1: every plain full-lattice application -- mul!, lqcd_bench_dslash -- that takes an eligible instance of the scalar-addressing kernel
  * walks its slabs backwards; read-only sweep_rev_active: did the last such launch),
+ * dslash_xshare (1 [default]: where an x-row of a parity is 16 sites (X = 32) and x is not partitioned, the x wave of the scalar-addressing Wilson kernel -- fp64, the instances of
+ * full-lattice applications and of the CG -- loads the opposite-parity chunk once and takes both x-neighbours from it by a lane shift through its own LDS slab: 27 instead of 39 loads,
+ * identical bits; 0: two loads.  Read-only xshare_active: did the last eligible launch take it),
+ * nt_centre (1 [default]: the update source of the scalar-addressing Wilson kernel's update and recurrence modes -- read once per launch at the centre, never a neighbour -- is a
+ * non-temporal load and stays out of the L2; a hint, identical bits; 0: plain load),
  * halo_fold (1 [default], round 5: where the collective timing picks the one-stream halo schedule 3, the stencil launch takes the boundary hops from the ghost
  * buffers itself -- no exterior kernel, for every operator and both precisions; read-only halo_fold_active), cg_persist (1 [default]: a staggered CG on an unpartitioned lattice of
  * at most 256 chunks of 64 sites runs as ONE launch -- initial residual and all iterations, two grid-wide synchronisations per iteration, every wait bounded: if the workgroups are not all resident (a busy GPU) x is left untouched, the solve is

@@ -341,6 +341,9 @@ static int* param_ptr(lqcd_ctx_s* c, const char* key) {
     if (!strcmp(key, "cg_sweep_alt_active")) return &c->tun.cg_sweep_alt_active;
     if (!strcmp(key, "dslash_sweep")) return &c->tun.dslash_sweep;
     if (!strcmp(key, "sweep_rev_active")) return &c->tun.sweep_rev_active;
+    if (!strcmp(key, "dslash_xshare")) return &c->tun.dslash_xshare;
+    if (!strcmp(key, "xshare_active")) return &c->tun.xshare_active;
+    if (!strcmp(key, "nt_centre")) return &c->tun.nt_centre;
     if (!strcmp(key, "cg_persist")) return &c->tun.cg_persist;
     if (!strcmp(key, "md_remap")) return &c->tun.md_remap;
     if (!strcmp(key, "staple_recon")) return &c->tun.staple_recon;

@@ -545,6 +545,11 @@ struct Tunables {
     int dslash_sweep = 0;     // measurement and tests: 1 reverses the sweep of every plain full-lattice application (op_apply_async: mul!, lqcd_bench_dslash) that takes
                               // an eligible instance of the scalar-addressing kernel
     int sweep_rev_active = 0; // read-only: 1 if the last launch of the scalar-addressing kernel walked its slabs backwards
+    int dslash_xshare = 1;    // scalar-addressing Wilson kernel (fp64, instances with the separate update source), XH = 16, x not partitioned: the x wave takes both x-neighbours
+                              // from ONE load of the opposite-parity chunk and a lane shift through its own LDS slab (27 instead of 39 loads; stencil.hip sdir_wave).  Identical bits; CG at 32^3x64 +2.7 % (profiles/r15_xshare_ab.log)
+    int xshare_active = 0;    // read-only: 1 if the last eligible launch of the scalar-addressing kernel took the x-share
+    int nt_centre = 1;        // scalar-addressing Wilson kernel, update and recurrence modes: the update source (read once per launch at the centre) is a non-temporal load: it
+                              // stays out of the L2 the neighbour spinors and links of a tile live in.  A hint; CG +0.7 % at steady clocks (profiles/r15_xshare_ab.log)
     int cg_skip_done = 1;     // fused CG: the first Dslash of an iteration checks the convergence flag as well (0: only the second does)
     int clover_transport = 0; // 1: build the clover sums by the plaquette-transport passes also on an unpartitioned lattice (tests)
     int stag_both = 0;            // 1: staggered split kernel issues the loads of both hops of a direction back to back (unpartitioned lattices)

@@ -375,6 +375,9 @@ struct PipeArgs {
     double* scal_w;
     real a, b;
     int nt_store;
+    int nt_centre;            // scalar-addressing kernel, RING instances: the update source (usrc: read once per launch, never a neighbour) is a non-temporal load (tunable nt_centre)
+    int xshare;               // scalar-addressing kernel, x wave of the RING instances (fp64 build): both x-neighbours from ONE load of the opposite-parity chunk (sdir_wave); set by
+                              // the host where XH == 16 -- an x-row is a 16-lane row of the chunk -- and x is not partitioned (tunable dslash_xshare)
     // scalar-addressing kernel, one workgroup per chunk (plain, update-mode and temporal-gauge instances): the slab of a workgroup is (pass, t) of the map below -- what the
     // eight XCDs work on at the same time -- numbered pass * LT + t in dispatch order.  sweep_rev: workgroup b runs the virtual block of slab nslab - 1 - q with its XCD, parity
     // and place inside the slab kept (StencilCall::sweep_rev)
@@ -775,6 +778,16 @@ __device__ inline void fold_unit_link(cd (&u)[9], bool face) {      // (called w
     }
 }
 
+// the link formats whose RING instances take the x-share (PipeArgs::xshare; sdir_wave) -- read by the kernel and by the host's report (xshare_active).  All three keep three
+// waves per SIMD without scratch with it (12-real and temporal gauge 162 VGPRs, 12 + delta 162, 18-real 166): none is excluded in the default fp64 build
+__host__ __device__ constexpr bool sdir_xshare_instance(bool r12, bool delta) {
+#if defined(LQCD_F32) || LQCD_SDIR_BOTH || LQCD_SDIR_GLDS
+    return false;
+#else
+    return true;
+#endif
+}
+
 // TG (plain fp64 12-real instances only): the links are the temporal-gauge copy (lqcd_gauge_s::data12t) -- a time-like link is the unit matrix unless its hop crosses
 // the seam t = T - 1 -> 0, which is what s.wf / s.wb say for MU = 3 (wave-uniform): the t wave loads no link and skips the two SU(3) products and the row-2
 // rebuild everywhere else.  The boundary sign stays with pipe_sign.
@@ -808,6 +821,12 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
     constexpr bool LATE_R = DELTA || !R12;            // fp64: the instances that would spill at 3 waves per SIMD with the old r held across the hops
 #endif
     constexpr bool RING = !DOT && !DW5 && !FOLD && !CINV;      // the instances with the separate update source and the recurrence mode (the others sit at their register caps)
+    // x-share (PipeArgs::xshare, XH == 16): lane i's x-neighbours are sites i / i + 1 (forward) and i - 1 / i (backward) of the opposite-parity chunk with this chunk's index,
+    // the wrap inside the lane's row of 16 (pipe_site).  The wave loads that chunk ONCE at the lane's own index, projects both ways at the source site, parks the 6 + 6 words in
+    // its own slab of the partial-sum area (idle until the hops are done; no other wave touches it: a wave-level fence, no barrier) and every lane reads its operands back at the
+    // neighbour's lane.  Projection and sign are the same operations on the same values, the sign stays with the receiving lane: the bits of the two-load path.
+    constexpr bool XS = MU == 0 && RING && sdir_xshare_instance(R12, DELTA);
+    const bool xs = XS && a_.xshare != 0;      // (wave-uniform: a kernel argument)
     const size_t gpar = (size_t)a.nch * 4 * NL * 64;
     const PipeSite s = pipe_site<MU, NL>(a, vblock, lane);
     cd xv[3] = {mk(0, 0), mk(0, 0), mk(0, 0)}, rv[3] = {mk(0, 0), mk(0, 0), mk(0, 0)};
@@ -826,7 +845,10 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
         if constexpr (!CINV) load_z();
     } else if (!LATE_R && a.upd_scal) {    // (18-real and 12 + delta links: their extra words take these registers during the hops; the old r is requested behind them)
 #pragma unroll
-        for (int cc = 0; cc < 3; cc++) rv[cc] = ld(boff(RING ? (s.p ? a.usrc[1] : a.usrc[0]) : (s.p ? a.dst[1] : a.dst[0]), s.own) + co12(3 * MU + cc));
+        for (int cc = 0; cc < 3; cc++) {
+            const real2* rp = boff(RING ? (s.p ? a.usrc[1] : a.usrc[0]) : (s.p ? a.dst[1] : a.dst[0]), s.own) + co12(3 * MU + cc);
+            rv[cc] = (RING && a.nt_centre) ? ld_nt(rp) : ld(rp);      // (the update source is read here and nowhere else in the launch)
+        }
     }
     constexpr bool LATE_X = (LATE_R && !R12 && !DOT) || (CINV && DOT);      // all 18 reals, and the dot instances with the clover blocks in the epilogue: the diagonal term's load moves behind the hops as well
     if (!LATE_X && a.a != real(0.0)) {
@@ -869,6 +891,55 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
         }
     }
     const size_t gslot = FOLD ? (size_t)(a.both ? s.p : 0) * 6 * (size_t)a.Fh[MU] + (size_t)s.fidx : 0;
+    if (xs) {
+#ifndef LQCD_F32
+        if constexpr (XS) {      // both hops of the x wave from one spinor load (scalar branch; the same link loads, products and signs as below)
+            {
+                cd sX[12], uF[9], dF[2];
+                load_comps12<0, 12, false>(sX, boff(s.p ? a.in[0] : a.in[1], s.own));
+                load_link_any<R12, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64);
+                if constexpr (DELTA) { dF[0] = ld(boff(a.gauge + (s.p ? gpar : 0), s.uf) + 6 * 64); dF[1] = ld(boff(a.gauge + (s.p ? gpar : 0), s.uf) + 7 * 64); }
+                project_regs<MU, SF>(h0, h1, sX);
+#pragma unroll
+                for (int c = 0; c < 3; c++) { part[0][c][lane] = mk2(h0[c].re, h0[c].im); part[0][3 + c][lane] = mk2(h1[c].re, h1[c].im); }
+                project_regs<MU, -SF>(h0, h1, sX);
+#pragma unroll
+                for (int c = 0; c < 3; c++) { part[0][6 + c][lane] = mk2(h0[c].re, h0[c].im); part[0][9 + c][lane] = mk2(h1[c].re, h1[c].im); }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // (this wave's own slab: the writes above against the reads at other lanes below)
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                const int lf = (int)(s.nf >> 4) & 63;      // the lane that holds the forward neighbour: i or i + 1, the wrap inside the row of 16
+#pragma unroll
+                for (int c = 0; c < 3; c++) { h0[c] = ld(&part[0][c][lf]); h1[c] = ld(&part[0][3 + c][lf]); }
+                finish_link<R12>(uF);
+                if constexpr (DELTA) add_delta_row2(uF, dF);
+                pipe_sign(h0, h1, s.sf);
+                su3_mv<false>(chi0, uF, h0);
+                su3_mv<false>(chi1, uF, h1);
+                reconstruct<MU, SF>(acc, chi0, chi1);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            {
+                cd uB[9], dB[2];
+                load_link_any<R12, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
+                if constexpr (DELTA) {
+                    const real2* db = boff(a.gauge + (s.p ? 0 : gpar), s.ub);
+                    dB[0] = NTB ? ld_nt(db + 6 * 64) : ld(db + 6 * 64);
+                    dB[1] = NTB ? ld_nt(db + 7 * 64) : ld(db + 7 * 64);
+                }
+                const int lb = (int)(s.nb >> 4) & 63;      // i - 1 or i
+#pragma unroll
+                for (int c = 0; c < 3; c++) { h0[c] = ld(&part[0][6 + c][lb]); h1[c] = ld(&part[0][9 + c][lb]); }
+                finish_link<R12>(uB);
+                if constexpr (DELTA) add_delta_row2(uB, dB);
+                pipe_sign(h0, h1, s.sb);
+                su3_mv<true>(chi0, uB, h0);
+                su3_mv<true>(chi1, uB, h1);
+                reconstruct<MU, -SF>(acc, chi0, chi1);
+            }
+        }
+#endif
+    } else {
     {
         cd sF[NS], uF[9], dF[2];
         if constexpr (FOLD && MU >= 1) fold_load_spinor<MU, NS, FF>(sF, boff(s.p ? a.in[0] : a.in[1], s.nf), a.gh_f[MU] + gslot, a.Fh[MU], gF);
@@ -959,6 +1030,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
         }
         reconstruct<MU, -SF>(acc, chi0, chi1);
     }
+    }
 #endif
     if constexpr (LATE_X) if (a.a != real(0.0)) {
 #pragma unroll
@@ -966,7 +1038,10 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
     }
     if constexpr (LATE_R && !DOT) if (a.upd_scal) {       // the LDS exchange and the barrier cover this load
 #pragma unroll
-        for (int cc = 0; cc < 3; cc++) rv[cc] = ld(boff(RING ? (s.p ? a.usrc[1] : a.usrc[0]) : (s.p ? a.dst[1] : a.dst[0]), s.own) + co12(3 * MU + cc));
+        for (int cc = 0; cc < 3; cc++) {
+            const real2* rp = boff(RING ? (s.p ? a.usrc[1] : a.usrc[0]) : (s.p ? a.dst[1] : a.dst[0]), s.own) + co12(3 * MU + cc);
+            rv[cc] = (RING && a.nt_centre) ? ld_nt(rp) : ld(rp);      // (the update source is read here and nowhere else in the launch)
+        }
     }
 #pragma unroll
     for (int j = 0; j < 12; j++) part[MU][j][lane] = mk2(acc[j].re, acc[j].im);
@@ -1797,6 +1872,8 @@ static PipeArgs make_pipe_args(lqcd_ctx_s* c, const KArgs& k, const StencilCall&
     a.norm_partial = k.norm_partial; a.upd_scal = k.upd_scal; a.skip = k.skip; a.scal_w = k.scal_w;
     a.a = k.a; a.b = k.b;
     a.nt_store = (k.nt & 4) != 0;
+    a.nt_centre = c->tun.nt_centre != 0;
+    a.xshare = 0;                      // (set by pipe_xshare_args for the launches of the RING instances)
     a.sweep_rev = 0; a.nslab = 0;      // (set by the one launch site that honours StencilCall::sweep_rev)
     a.nvirt = k.nblocks; a.both = s.parity_mode == 2; a.pmode = s.parity_mode == 2 ? 0 : s.parity_mode;
     a.XH = k.g.XH; a.L1 = k.g.L[1]; a.L2 = k.g.L[2]; a.LT = k.g.L[3]; a.nch = k.g.nch; a.dXH = k.g.dXH;
@@ -1834,6 +1911,16 @@ static void pipe_sweep_args(lqcd_ctx_s* c, const KArgs& k, const StencilCall& s,
     if (!plain || !map_ok) return;
     a.sweep_rev = s.sweep_rev ? 1 : 0;
     c->tun.sweep_rev_active = a.sweep_rev;
+}
+
+// The x-share of the scalar-addressing kernel's x wave (sdir_wave, PipeArgs::xshare): offered by the RING instances of the fp64 build, one workgroup per chunk, where an
+// x-row of a parity is exactly one 16-lane row of a chunk (XH == 16) and the x direction is not partitioned.  Every other geometry takes the two-load path.
+static void pipe_xshare_args(lqcd_ctx_s* c, const KArgs& k, const StencilCall& s, bool delta, PipeArgs& a) {
+    a.xshare = 0;
+    if (kF32Build || c->tun.dslash_pipe != 2 || s.dw_ls > 1 || s.fold) return;
+    const bool inst = sdir_xshare_instance(k.gauge12 != nullptr, delta);
+    a.xshare = (inst && c->tun.dslash_xshare && k.g.XH == 16 && !k.g.part[0]) ? 1 : 0;
+    c->tun.xshare_active = a.xshare;
 }
 
 static HArgs make_hargs(lqcd_ctx_s* c, const StencilCall& s);
@@ -2030,6 +2117,7 @@ int launch_stencil_interior(lqcd_ctx_s* c, const StencilCall& s) {
             const dim3 pg(c->tun.dslash_pipe == 1 ? wilson_pipe_grid(c, k.nblocks, s.prec) : c->tun.dslash_pipe == 3 ? k.nblocks / a.per_wg : k.nblocks), pb(256);
             const bool ntb = (k.nt & 1) != 0;
             pipe_sweep_args(c, k, s, delta, a);      // (read by the launches of the last branch below only)
+            pipe_xshare_args(c, k, s, delta, a);     // (the 12 + delta launch and the last branch)
 #ifndef LQCD_F32
             if (s.dw_ls > 1) {      // Domainwall: the L5 slices in one launch, fifth-direction hops in the epilogue (plain loads for the backward link: it is re-used by the next slice)
                 if (c->tun.dslash_pipe != 2 || delta) { set_error("stencil: the five-dimensional launch needs the scalar-addressing kernel in its plain mode"); return LQCD_ERR_UNSUPPORTED; }
