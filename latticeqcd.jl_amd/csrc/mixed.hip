@@ -722,7 +722,14 @@ static int inner_bicgstab_eo32(lqcd_op_s* op, const Eo32& m, size_t nh, int dg, 
     }
     int check_every = first_burst > 0 ? std::min(first_burst, 64) : std::max(4, std::min(op->bicg_hint - 1, 64));
     double done = 0.0;
+    // A chain asked for more than fp32 can give -- on an ill-conditioned system rounding puts a floor under its recursive residual well above 1e-6 -- would wander
+    // at that floor until the whole iteration budget is gone and none is left for the fp64 chain that finishes the solve.  It stops once the residual has set no
+    // new low (by a factor 2) for twice as long as it took to reach the last one, at least 128 iterations; the caller's true residual decides what follows.
+    const int it_start = it;
+    int it_low = it;
+    double low = HUGE_VAL;
     while (done == 0.0 && it < maxiter) {
+        if (it - it_low >= std::max(128, 2 * (it_low - it_start))) break;
         const int burst = std::min(check_every, maxiter - it);
         check_every = 2;
         for (int q = 0; q < burst; q++, enq++) {
@@ -767,6 +774,7 @@ static int inner_bicgstab_eo32(lqcd_op_s* op, const Eo32& m, size_t nh, int dg, 
         HIPCHK(hipStreamSynchronize(c->stream));
         it = (int)c->h_scal[B_ITERS - B_RHO];
         done = c->h_scal[B_DONE - B_RHO];
+        if (c->h_scal[B_RES - B_RHO] < 0.5 * low) { low = c->h_scal[B_RES - B_RHO]; it_low = it; }
     }
     *iters = it;
     if (full_stop) *full_stop = (done == 1.0 && c->h_scal[B_HALF - B_RHO] == 0.0) ? 1 : 0;      // stopped behind a whole iteration: the chain can go on after a reliable update

@@ -2,7 +2,8 @@
 update source and recurrence mode).  D p is formed by s' = D r' + beta s from the residual D^+ has just written, p and x are brought up to date once per K iterations.
 Compared with cg_fused = 2 of the same library to the 1e-12 the project holds across cg_fused forms (tests/test_gpu_tgauge.py), iteration counts within +-1;
 bit for bit wherever the same launches run.  16.8.8.4 (cg_small = 0, cg_tgauge = 2: seam slices are half the lattice, 64 workgroups) and 16.16.16.32 (default
-settings: 2048 workgroups, the temporal-gauge path as the flagship lattice takes it)."""
+settings: 2048 workgroups, the temporal-gauge path as the flagship lattice takes it).
+The same forms on an ill-conditioned system (1073 iterations, accuracy held against the oracle): tests/test_gpu_hard_solves.py."""
 import ctypes as C
 
 import numpy as np

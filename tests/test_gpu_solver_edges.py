@@ -1,5 +1,7 @@
 """Solver edge cases: zero right-hand side, exact initial guess, non-finite input, iteration caps that are not a multiple of the
-polling burst -- for the CG, BiCGStab (plain and even-odd), multi-shift and mixed-precision solvers."""
+polling burst -- for the CG, BiCGStab (plain and even-odd), multi-shift and mixed-precision solvers.
+The same solvers on ill-conditioned systems (an exhausted 500-iteration solve, the staggered parity block at m = 0.005, the merged BiCGStab update near kappa_c):
+tests/test_gpu_hard_solves.py."""
 import numpy as np
 from conftest import rel_err
 import pytest
