@@ -411,6 +411,9 @@ extern "C" int lqcd_ctx_set_param(lqcd_ctx_t c, const char* key, int value) {
     if (!strcmp(key, "bicg_fused")) ARGCHK(value != 3, "bicg_fused must be 0, 1, 2 or 4 (3, the grid-barrier form, was measured slower and removed)");
     if (!strcmp(key, "halo_inject_us")) ARGCHK(value >= 0 && value <= 100000, "halo_inject_us: 0..100000");
     if ((!strcmp(key, "lazy_links") || !strcmp(key, "lazy_merge")) && !value) LQCHK(links_flush_of(c));      // switching to eager calls: what is recorded runs now
+    // a recorded update runs under the settings in force when it was ASKED for (md_reunitarize, lazy_merge, gauge_recon, ... are read when it launches):
+    // a key that changes while something is recorded runs the records first
+    if (*p != value) LQCHK(links_flush_of(c));
     *p = value;
     return LQCD_OK;
 }
