@@ -24,7 +24,7 @@ namespace lqcd {
 constexpr int KE = 3;
 // s = r - alpha v ; partial |s|^2          (fold: alpha = rho / <r0, v> from the partials of the Schur operator's epilogue)
 __global__ __launch_bounds__(UB) void bicgf_s(BicgF a, double2* __restrict__ s, const double2* __restrict__ r, const double2* __restrict__ v, size_t n) {
-    if (a.sc[B_DONE] != 0.0) return;
+    if (a.sc[B_DONE] != 0.0) { if (blockIdx.x == 0 && threadIdx.x == 0) a.sc[B_XDONE] = 1.0; return; }      // raised by an EARLIER launch: its update is complete (B_XDONE, lqcd_internal.h)
     const size_t i0 = (size_t)blockIdx.x * UB + threadIdx.x, stride = (size_t)gridDim.x * UB;
     double2 pr[KE], pv[KE];
 #pragma unroll
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(UB) void bicgf_s(BicgF a, double2* __restrict__ s, 
         double t1[1];
         block_sum_partials<1>(a.pin3, a.pin3_n, t1);
         if (blockIdx.x == 0 && threadIdx.x == 0) { a.sc[B_RES] = t1[0]; a.sc[B_RR] = t1[0]; }
-        if (t1[0] < a.sc[B_EPS]) { if (blockIdx.x == 0 && threadIdx.x == 0) a.sc[B_DONE] = 1.0; return; }
+        if (t1[0] < a.sc[B_EPS]) { if (blockIdx.x == 0 && threadIdx.x == 0) { a.sc[B_DONE] = 1.0; a.sc[B_XDONE] = 1.0; } return; }      // (the update it judges was the last launch's)
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) { a.sc[B_R0V] = r0v.re; a.sc[B_R0V + 1] = r0v.im; a.sc[B_ALPHA] = al.re; a.sc[B_ALPHA + 1] = al.im; }
     const double ar = al.re, ai = al.im;
@@ -164,9 +164,11 @@ __global__ __launch_bounds__(UB) void bicgf_p(BicgF a, double2* __restrict__ p, 
 // equal those of the other forms up to the rounding of the two recurrences (fp64: ~1e-16 of |r0| |r| per iteration, tests/test_gpu_solver_edges.py); the
 // stopping test trusts the recurrence for |r'|^2 only while it is free of cancellation (|r'|^2 > 1e-6 |s|^2), otherwise this launch also sums the |r'|^2 it
 // writes and the NEXT iteration's first streaming kernel decides (bicgf_s, a.pin3; the two hops in between are wasted once).
+// The done flag travels in two stages: the lead raises B_DONE here (hops, bicgf_s and the host look at it), bicgf_s of the next iteration promotes it to B_XDONE, and
+// only B_XDONE turns this launch into a no-op -- a workgroup that starts after the lead's store still applies the last update.
 __global__ __launch_bounds__(UB) void bicgf_xrp_rec(BicgF a, double2* __restrict__ x, double2* __restrict__ r, double2* __restrict__ p, const double2* __restrict__ s,
                                                      const double2* __restrict__ t, const double2* __restrict__ v, size_t n) {
-    if (a.sc[B_DONE] != 0.0) return;
+    if (a.sc[B_XDONE] != 0.0) return;      // NOT B_DONE: the lead of this launch raises it below while other workgroups have not started, and they owe x the converging iteration's update
     const size_t i0 = (size_t)blockIdx.x * UB + threadIdx.x, stride = (size_t)gridDim.x * UB;
     double2 pp[KE], ps[KE], pt[KE], px[KE], pv_[KE];
 #pragma unroll
@@ -263,7 +265,7 @@ __global__ __launch_bounds__(64) void bicgf_init_scal(const double* __restrict__
     if (threadIdx.x == 0) {
         for (int j = B_RHO; j < B_END; j++) sc[j] = 0.0;
         sc[B_RHO] = rr; sc[B_RHOB] = rr; sc[B_EPS] = eps; sc[B_RES] = rr;
-        if (rr < eps) sc[B_DONE] = 1.0;
+        if (rr < eps) { sc[B_DONE] = 1.0; sc[B_XDONE] = 1.0; }
     }
 }
 

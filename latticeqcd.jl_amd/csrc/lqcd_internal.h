@@ -329,8 +329,11 @@ enum { S_RED0 = 0, S_RR = 8, S_PQ = 9, S_ALPHA = 10, S_BETA = 11, S_DONE = 12, S
        S_BHIST = 72 };      // S_BHIST .. +7: cg_fused = 3, the beta of the pending iterations (the host never reads either history)
 // BiCGStab block (complex scalars are two consecutive doubles; B_TS..B_TT and B_RR..B_RHO1 are filled by one 3-value reduction)
 enum { B_RHO = 24, B_R0V = 26, B_VV = 28, B_ALPHA = 29, B_SS = 31, B_TS = 32, B_TT = 34, B_OMEGA = 35, B_RR = 37, B_RHO1 = 38, B_BETA = 40,
-       B_DONE = 42, B_ITERS = 43, B_EPS = 44, B_HALF = 45, B_RES = 46, B_RHOB = 47, B_TS5 = 49, B_UNSURE = 54, B_END = 55 };   // B_TS5: <t, s>, |t|^2, <r0, t> of the merged chain (bicg_fused = 4), one 5-value reduction;      // B_R0V..B_VV, B_TS..B_TT and B_RR..B_RHO1 are filled by one
+       B_DONE = 42, B_ITERS = 43, B_EPS = 44, B_HALF = 45, B_RES = 46, B_RHOB = 47, B_TS5 = 49, B_UNSURE = 54, B_XDONE = 55, B_END = 56 };   // B_TS5: <t, s>, |t|^2, <r0, t> of the merged chain (bicg_fused = 4), one 5-value reduction;      // B_R0V..B_VV, B_TS..B_TT and B_RR..B_RHO1 are filled by one
                                                                                                      // 3-value reduction each; B_RHOB: second rho slot of the fused chain
+// B_XDONE (merged chain, bicg_fused = 4): "the update of the converging iteration has been applied".  The merged update launch raises B_DONE while its other workgroups
+// still have the last x += alpha p + omega s to do, so it tests at entry THIS word, which the first streaming kernel of the next iteration raises once it meets B_DONE
+// (the CG's S_DONE / S_XDONE): no launch tests at entry a word that one of its own workgroups writes.
 __device__ inline void cg_scalar_step(double* s, int op) {
     if (op == 1) {
         if (s[S_DONE] != 0.0) { s[S_XDONE] = 1.0; return; }

@@ -471,7 +471,7 @@ __device__ inline void cdot4(double& re, double& im, const float4 z, const float
 // s = r - alpha v ; partial |s|^2
 template <bool PAIR>
 __global__ __launch_bounds__(UB) void bicgf32_s(BicgF a, float4* __restrict__ s, const float4* __restrict__ r, const float4* __restrict__ v, size_t n4) {
-    if (a.sc[B_DONE] != 0.0) return;
+    if (a.sc[B_DONE] != 0.0) { if (blockIdx.x == 0 && threadIdx.x == 0) a.sc[B_XDONE] = 1.0; return; }      // raised by an earlier launch: promoted for the merged update (B_XDONE, lqcd_internal.h)
     const size_t i0 = (size_t)blockIdx.x * UB + threadIdx.x, stride = (size_t)gridDim.x * UB;
     float4 pr[2], pv[2];
 #pragma unroll
@@ -484,7 +484,7 @@ __global__ __launch_bounds__(UB) void bicgf32_s(BicgF a, float4* __restrict__ s,
         double t1[1];
         block_sum_partials<1>(a.pin3, a.pin3_n, t1);
         if (blockIdx.x == 0 && threadIdx.x == 0) { a.sc[B_RES] = t1[0]; a.sc[B_RR] = t1[0]; }
-        if (t1[0] < a.sc[B_EPS]) { if (blockIdx.x == 0 && threadIdx.x == 0) a.sc[B_DONE] = 1.0; return; }
+        if (t1[0] < a.sc[B_EPS]) { if (blockIdx.x == 0 && threadIdx.x == 0) { a.sc[B_DONE] = 1.0; a.sc[B_XDONE] = 1.0; } return; }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) { a.sc[B_R0V] = r0v.re; a.sc[B_R0V + 1] = r0v.im; a.sc[B_ALPHA] = al.re; a.sc[B_ALPHA + 1] = al.im; }
     const float ar = -(float)al.re, ai = -(float)al.im;
@@ -556,7 +556,7 @@ __global__ __launch_bounds__(UB) void bicgf32_p(BicgF a, float4* __restrict__ p,
     const double rr = half ? a.sc[B_SS] : rrn;
     const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
     if (a.cont) {      // r is the true residual of a reliable update, rho1 = <r0, r> with it: no test, the chain is armed for the next stretch
-        if (lead) { a.sc[B_RES] = rrn; a.sc[B_RR] = rrn; a.sc[B_RHO1] = rho1.re; a.sc[B_RHO1 + 1] = rho1.im; a.sc[B_EPS] = a.cont_eps; a.sc[B_DONE] = 0.0; }
+        if (lead) { a.sc[B_RES] = rrn; a.sc[B_RR] = rrn; a.sc[B_RHO1] = rho1.re; a.sc[B_RHO1 + 1] = rho1.im; a.sc[B_EPS] = a.cont_eps; a.sc[B_DONE] = 0.0; a.sc[B_XDONE] = 0.0; }
     } else {
         if (lead) { a.sc[B_ITERS] += 1.0; a.sc[B_RES] = rr; a.sc[B_RR] = rrn; a.sc[B_RHO1] = rho1.re; a.sc[B_RHO1 + 1] = rho1.im; }
         if (half || rr < a.sc[B_EPS]) { if (lead) a.sc[B_DONE] = 1.0; return; }
@@ -580,7 +580,7 @@ __global__ __launch_bounds__(UB) void bicgf32_p(BicgF a, float4* __restrict__ p,
 template <bool PAIR>
 __global__ __launch_bounds__(UB) void bicgf32_xrp_rec(BicgF a, float4* __restrict__ x, float4* __restrict__ r, float4* __restrict__ p, const float4* __restrict__ s,
                                                        const float4* __restrict__ t, const float4* __restrict__ v, size_t n4) {
-    if (a.sc[B_DONE] != 0.0) return;
+    if (a.sc[B_XDONE] != 0.0) return;      // not B_DONE, which the lead of this launch raises (bicgstab_eo.hip bicgf_xrp_rec)
     const size_t i0 = (size_t)blockIdx.x * UB + threadIdx.x, stride = (size_t)gridDim.x * UB;
     float4 pp[2], ps[2], pt[2], px[2], pv_[2];
 #pragma unroll

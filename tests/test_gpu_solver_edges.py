@@ -333,6 +333,9 @@ def test_evenodd_bicgstab_fused_chain_is_bit_identical_to_the_unfolded_one(lq, o
     x = b.similar()
     it, rr = lq.solve_DinvX_(x, D, b, return_info=True)
     assert it <= 2 and rr < 1e-6
+    # ... and x is the oracle's half-step iterate (x += alpha p alone), not merely some x with a small reported residual (tests/test_gpu_solve_endings.py)
+    xo, ito, rro, st = orc.wilson_bicgstab_eo(U.download(), b.download(), L, 0.01, 1.0, (1, 1, 1, -1), False, eps=1e-6)
+    assert st == 0 and it == ito and abs(rr - rro) <= 1e-8 * rro and rel_err(x.download(), xo) < 1e-10
     lq.clear_fermion_(b)
     lq.clear_fermion_(x)
     it, rr = lq.solve_DinvX_(x, D, b, return_info=True)
