@@ -111,6 +111,10 @@ int lqcd_ctx_sync(lqcd_ctx_t ctx);
  * dslash_xshare (1 [default]: where an x-row of a parity is 16 sites (X = 32) and x is not partitioned, the x wave of the scalar-addressing Wilson kernel -- fp64, the instances of
  * full-lattice applications and of the CG -- loads the opposite-parity chunk once and takes both x-neighbours from it by a lane shift through its own LDS slab: 27 instead of 39 loads,
  * identical bits; 0: two loads.  Read-only xshare_active: did the last eligible launch take it),
+ * dslash_yshare (1 [default]: where the x-share is taken, Y is a multiple of 4 and y is not partitioned, the y wave of the 12-real instances -- plain, temporal gauge, 12 + delta --
+ * takes the y-neighbours that lie in that same chunk (three of the four 16-site rows each way) from the x wave's load, handed over through LDS behind one workgroup barrier,
+ * and loads only the edge row of each hop itself; identical bits; 0: two full loads; dslash_xshare = 0 switches it off as well.  Read-only yshare_active: did the last
+ * eligible launch take it),
  * nt_centre (1 [default]: the update source of the scalar-addressing Wilson kernel's update and recurrence modes -- read once per launch at the centre, never a neighbour -- is a
  * non-temporal load and stays out of the L2; a hint, identical bits; 0: plain load),
  * halo_fold (1 [default], round 5: where the collective timing picks the one-stream halo schedule 3, the stencil launch takes the boundary hops from the ghost

@@ -343,6 +343,8 @@ static int* param_ptr(lqcd_ctx_s* c, const char* key) {
     if (!strcmp(key, "sweep_rev_active")) return &c->tun.sweep_rev_active;
     if (!strcmp(key, "dslash_xshare")) return &c->tun.dslash_xshare;
     if (!strcmp(key, "xshare_active")) return &c->tun.xshare_active;
+    if (!strcmp(key, "dslash_yshare")) return &c->tun.dslash_yshare;
+    if (!strcmp(key, "yshare_active")) return &c->tun.yshare_active;
     if (!strcmp(key, "nt_centre")) return &c->tun.nt_centre;
     if (!strcmp(key, "cg_persist")) return &c->tun.cg_persist;
     if (!strcmp(key, "md_remap")) return &c->tun.md_remap;

@@ -551,6 +551,10 @@ struct Tunables {
     int dslash_xshare = 1;    // scalar-addressing Wilson kernel (fp64, instances with the separate update source), XH = 16, x not partitioned: the x wave takes both x-neighbours
                               // from ONE load of the opposite-parity chunk and a lane shift through its own LDS slab (27 instead of 39 loads; stencil.hip sdir_wave).  Identical bits; CG at 32^3x64 +2.7 % (profiles/r15_xshare_ab.log)
     int xshare_active = 0;    // read-only: 1 if the last eligible launch of the scalar-addressing kernel took the x-share
+    int dslash_yshare = 1;    // with the x-share, L1 a multiple of 4, y not partitioned: the y wave takes the in-chunk y-neighbours (three of four 16-lane rows each way) from the chunk
+                              // the x wave has loaded, handed over through the y wave's LDS slab behind one workgroup barrier, and loads only the edge row of each hop itself
+                              // (stencil.hip sdir_wave).  Identical bits; off whenever dslash_xshare is; CG at 32^3x64 +3.3 % (profiles/r16_yshare_ab.log)
+    int yshare_active = 0;    // read-only: 1 if the last eligible launch of the scalar-addressing kernel took the y-share
     int nt_centre = 1;        // scalar-addressing Wilson kernel, update and recurrence modes: the update source (read once per launch at the centre) is a non-temporal load: it
                               // stays out of the L2 the neighbour spinors and links of a tile live in.  A hint; CG +0.7 % at steady clocks (profiles/r15_xshare_ab.log)
     int cg_skip_done = 1;     // fused CG: the first Dslash of an iteration checks the convergence flag as well (0: only the second does)

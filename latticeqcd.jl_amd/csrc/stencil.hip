@@ -378,6 +378,8 @@ struct PipeArgs {
     int nt_centre;            // scalar-addressing kernel, RING instances: the update source (usrc: read once per launch, never a neighbour) is a non-temporal load (tunable nt_centre)
     int xshare;               // scalar-addressing kernel, x wave of the RING instances (fp64 build): both x-neighbours from ONE load of the opposite-parity chunk (sdir_wave); set by
                               // the host where XH == 16 -- an x-row is a 16-lane row of the chunk -- and x is not partitioned (tunable dslash_xshare)
+    int yshare;               // with xshare: the y wave takes its in-chunk neighbours from the chunk the x wave has loaded, through LDS behind one workgroup barrier that all four
+                              // waves execute (sdir_wave); set by the host where also L1 % 4 == 0 and y is not partitioned (tunable dslash_yshare)
     // scalar-addressing kernel, one workgroup per chunk (plain, update-mode and temporal-gauge instances): the slab of a workgroup is (pass, t) of the map below -- what the
     // eight XCDs work on at the same time -- numbered pass * LT + t in dispatch order.  sweep_rev: workgroup b runs the virtual block of slab nslab - 1 - q with its XCD, parity
     // and place inside the slab kept (StencilCall::sweep_rev)
@@ -788,6 +790,10 @@ __host__ __device__ constexpr bool sdir_xshare_instance(bool r12, bool delta) {
 #endif
 }
 
+// the link formats whose RING instances take the y-share on top (PipeArgs::yshare): the 12-real ones -- temporal gauge and plain 168 VGPRs, 12 + delta 166, three waves per
+// SIMD without scratch.  The 18-real instance (166 with the x-share alone) spills 4 VGPRs with it and keeps today's code
+__host__ __device__ constexpr bool sdir_yshare_instance(bool r12, bool delta) { return r12 && sdir_xshare_instance(r12, delta); }
+
 // TG (plain fp64 12-real instances only): the links are the temporal-gauge copy (lqcd_gauge_s::data12t) -- a time-like link is the unit matrix unless its hop crosses
 // the seam t = T - 1 -> 0, which is what s.wf / s.wb say for MU = 3 (wave-uniform): the t wave loads no link and skips the two SU(3) products and the row-2
 // rebuild everywhere else.  The boundary sign stays with pipe_sign.
@@ -827,6 +833,16 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
     // neighbour's lane.  Projection and sign are the same operations on the same values, the sign stays with the receiving lane: the bits of the two-load path.
     constexpr bool XS = MU == 0 && RING && sdir_xshare_instance(R12, DELTA);
     const bool xs = XS && a_.xshare != 0;      // (wave-uniform: a kernel argument)
+    // y-share (PipeArgs::yshare, with the x-share; XH == 16, L1 % 4 == 0): a chunk is four y-rows of 16 lanes, so lane i's y-neighbours i + 16 (rows 0-2) and i - 16 (rows 1-3)
+    // lie in the opposite-parity chunk with this chunk's index -- the chunk the x wave holds in sX.  The x wave stores its twelve raw words to part[1] (the y wave's slab, idle until
+    // the y wave's hops are done), releases them and arrives at a workgroup barrier; every other wave arrives right behind the issue of its forward operands, with no wait on a
+    // load.  Behind it the y wave reads the in-chunk operands at lane +- 16 and loads only row 3's forward and row 0's backward neighbour -- the rows of the neighbouring chunks --
+    // itself, in the phase that consumes them.  Projection and sign stay on the receiving lane: the operations and values of the two-load path.  The barrier sits under the
+    // kernel arguments alone, behind the workgroup-uniform early return: all four waves of a workgroup execute it or none does.
+    constexpr bool YSI = RING && sdir_yshare_instance(R12, DELTA);
+    const bool ysh = YSI && a_.xshare != 0 && a_.yshare != 0;      // (wave-uniform, and the same value in the four waves)
+    constexpr bool YS = MU == 1 && YSI;
+    const bool ys = YS && ysh;
     const size_t gpar = (size_t)a.nch * 4 * NL * 64;
     const PipeSite s = pipe_site<MU, NL>(a, vblock, lane);
     cd xv[3] = {mk(0, 0), mk(0, 0), mk(0, 0)}, rv[3] = {mk(0, 0), mk(0, 0), mk(0, 0)};
@@ -891,7 +907,58 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
         }
     }
     const size_t gslot = FOLD ? (size_t)(a.both ? s.p : 0) * 6 * (size_t)a.Fh[MU] + (size_t)s.fidx : 0;
-    if (xs) {
+    if (ys) {
+#ifndef LQCD_F32
+        if constexpr (YS) {      // the y wave's in-chunk operands from the x wave's load (scalar branch; a straight-line arm of its own: the same link loads, products and signs as below)
+            const int row = lane >> 4;
+            {
+                cd sF[12], uF[9], dF[2];
+                if (row == 3) load_comps12<0, 12, false>(sF, boff(s.p ? a.in[0] : a.in[1], s.nf));      // row 0 of the next chunk in y (the wrap: of the plane's first)
+                load_link_any<R12, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64);
+                if constexpr (DELTA) { dF[0] = ld(boff(a.gauge + (s.p ? gpar : 0), s.uf) + 6 * 64); dF[1] = ld(boff(a.gauge + (s.p ? gpar : 0), s.uf) + 7 * 64); }
+                asm volatile("" ::: "memory");
+                __builtin_amdgcn_s_barrier();      // the x wave's chunk is in part[1] (this wave has written no LDS: nothing to wait for in front)
+                asm volatile("" ::: "memory");
+                if (row != 3) {
+#pragma unroll
+                    for (int j = 0; j < 12; j++) sF[j] = ld(&part[1][j][lane + 16]);
+                }
+                finish_link<R12>(uF);
+                if constexpr (DELTA) add_delta_row2(uF, dF);
+                project_regs<MU, SF>(h0, h1, sF);
+                pipe_sign(h0, h1, s.sf);
+                su3_mv<false>(chi0, uF, h0);
+                su3_mv<false>(chi1, uF, h1);
+                reconstruct<MU, SF>(acc, chi0, chi1);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            {
+                cd sB[12], uB[9], dB[2];
+                if (row == 0) load_comps12<0, 12, false>(sB, boff(s.p ? a.in[0] : a.in[1], s.nb));      // row 3 of the previous chunk in y
+                load_link_any<R12, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
+                if constexpr (DELTA) {
+                    const real2* db = boff(a.gauge + (s.p ? 0 : gpar), s.ub);
+                    dB[0] = NTB ? ld_nt(db + 6 * 64) : ld(db + 6 * 64);
+                    dB[1] = NTB ? ld_nt(db + 7 * 64) : ld(db + 7 * 64);
+                }
+                if (row != 0) {
+#pragma unroll
+                    for (int j = 0; j < 12; j++) sB[j] = ld(&part[1][j][lane - 16]);
+                }
+                finish_link<R12>(uB);
+                if constexpr (DELTA) add_delta_row2(uB, dB);
+                project_regs<MU, -SF>(h0, h1, sB);
+                pipe_sign(h0, h1, s.sb);
+                su3_mv<true>(chi0, uB, h0);
+                su3_mv<true>(chi1, uB, h1);
+                reconstruct<MU, -SF>(acc, chi0, chi1);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // (this wave's own slab from here on: its reads at other lanes above against the partial sums below)
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+#endif
+    } else if (xs) {
 #ifndef LQCD_F32
         if constexpr (XS) {      // both hops of the x wave from one spinor load (scalar branch; the same link loads, products and signs as below)
             {
@@ -899,6 +966,13 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
                 load_comps12<0, 12, false>(sX, boff(s.p ? a.in[0] : a.in[1], s.own));
                 load_link_any<R12, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64);
                 if constexpr (DELTA) { dF[0] = ld(boff(a.gauge + (s.p ? gpar : 0), s.uf) + 6 * 64); dF[1] = ld(boff(a.gauge + (s.p ? gpar : 0), s.uf) + 7 * 64); }
+                if (ysh) {      // y-share: the raw chunk to the y wave's slab, first of all -- the other three waves are held at the barrier until it is there
+#pragma unroll
+                    for (int j = 0; j < 12; j++) part[1][j][lane] = mk2(sX[j].re, sX[j].im);
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // workgroup-scope release of the LDS writes; no wait on the link load in flight
+                    __builtin_amdgcn_s_barrier();
+                    asm volatile("" ::: "memory");
+                }
                 project_regs<MU, SF>(h0, h1, sX);
 #pragma unroll
                 for (int c = 0; c < 3; c++) { part[0][c][lane] = mk2(h0[c].re, h0[c].im); part[0][3 + c][lane] = mk2(h1[c].re, h1[c].im); }
@@ -947,6 +1021,13 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
         if constexpr (TG && MU == 3) { if (s.wf) load_link_any<R12, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64); }      // (scalar branch)
         else load_link_any<R12, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64);
         if constexpr (DELTA) { dF[0] = ld(boff(a.gauge + (s.p ? gpar : 0), s.uf) + 6 * 64); dF[1] = ld(boff(a.gauge + (s.p ? gpar : 0), s.uf) + 7 * 64); }
+        if constexpr (YSI && MU >= 2) {      // y-share: the z and t waves arrive at its barrier with their forward operands in flight (no LDS access of theirs to order, no wait on a load)
+            if (ysh) {
+                asm volatile("" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+            }
+        }
 #if LQCD_SDIR_GLDS
         // The backward neighbour's spinor goes global -> LDS with the asynchronous copy of gfx950 (global_load_lds_dwordx4: wave-uniform LDS base +
         // 16 B x lane, exactly the [component][lane] slab this wave owns in the partial-sum area, which nobody touches before the hops are done):
@@ -1873,7 +1954,7 @@ static PipeArgs make_pipe_args(lqcd_ctx_s* c, const KArgs& k, const StencilCall&
     a.a = k.a; a.b = k.b;
     a.nt_store = (k.nt & 4) != 0;
     a.nt_centre = c->tun.nt_centre != 0;
-    a.xshare = 0;                      // (set by pipe_xshare_args for the launches of the RING instances)
+    a.xshare = 0; a.yshare = 0;        // (set by pipe_xshare_args for the launches of the RING instances)
     a.sweep_rev = 0; a.nslab = 0;      // (set by the one launch site that honours StencilCall::sweep_rev)
     a.nvirt = k.nblocks; a.both = s.parity_mode == 2; a.pmode = s.parity_mode == 2 ? 0 : s.parity_mode;
     a.XH = k.g.XH; a.L1 = k.g.L[1]; a.L2 = k.g.L[2]; a.LT = k.g.L[3]; a.nch = k.g.nch; a.dXH = k.g.dXH;
@@ -1916,11 +1997,15 @@ static void pipe_sweep_args(lqcd_ctx_s* c, const KArgs& k, const StencilCall& s,
 // The x-share of the scalar-addressing kernel's x wave (sdir_wave, PipeArgs::xshare): offered by the RING instances of the fp64 build, one workgroup per chunk, where an
 // x-row of a parity is exactly one 16-lane row of a chunk (XH == 16) and the x direction is not partitioned.  Every other geometry takes the two-load path.
 static void pipe_xshare_args(lqcd_ctx_s* c, const KArgs& k, const StencilCall& s, bool delta, PipeArgs& a) {
-    a.xshare = 0;
+    a.xshare = 0; a.yshare = 0;
     if (kF32Build || c->tun.dslash_pipe != 2 || s.dw_ls > 1 || s.fold) return;
     const bool inst = sdir_xshare_instance(k.gauge12 != nullptr, delta);
     a.xshare = (inst && c->tun.dslash_xshare && k.g.XH == 16 && !k.g.part[0]) ? 1 : 0;
     c->tun.xshare_active = a.xshare;
+    // the y-share on top of it: a chunk is four whole y-rows (XH == 16, L1 % 4 == 0), so rows 0-2 / 1-3 find their forward / backward y-neighbour in the x wave's chunk; y is
+    // not partitioned (the edge rows wrap inside the rank).  Off whenever the x-share is
+    a.yshare = (a.xshare && sdir_yshare_instance(k.gauge12 != nullptr, delta) && c->tun.dslash_yshare && k.g.L[1] % 4 == 0 && !k.g.part[1]) ? 1 : 0;
+    c->tun.yshare_active = a.yshare;
 }
 
 static HArgs make_hargs(lqcd_ctx_s* c, const StencilCall& s);
