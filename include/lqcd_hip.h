@@ -104,6 +104,12 @@ int lqcd_ctx_sync(lqcd_ctx_t ctx);
  * residuals of a batch in a ring and brings p and x up to date once per K iterations in one streaming launch; the recurrence restarts from an exact D p there.  2064 instead of
  * 2400 bytes per site and iteration at K = 4 (1992 at K = 8), K - 2 more work vectors; the iterates equal those of cg_fused = 2 to rounding; everything else runs as cg_fused = 2.
  * Read-only cg_rring_active: the K in use by the last CG set-up, 0 if the form did not apply),
+ * cg_rring_mult (cg_fused = 3; M = 4 [default], 1 or 2, other values are refused: the residual ring has K M <= 32 slots, p and x are brought up to date and the recurrence
+ * restarts every K M iterations -- 1944 / 1920 bytes per site and iteration at K M = 16 / 32, K M - 2 more work vectors; M is halved while the scratch pool cannot supply
+ * them; a context that never set the key keeps M = 1 on launch-bound lattices (at most 1024 stencil workgroups); with graph = 1 a captured burst is max(8, K M) iterations.
+ * Read-only cg_rring_depth_active: the K M in use by the last CG set-up, 0 if the form did not apply),
+ * scratch_max (0 [default]: no limit; n > 0: the context's pool of work fields holds at most n -- a memory budget; a solver that wants more falls back to a form that
+ * needs fewer or fails as on an allocation failure),
  * cg_sweep_alt (1 [default]: in a Wilson CG that runs in temporal gauge every D^+ launch walks the (pass, t) slabs of the XCD tile sweep backwards, so that each stencil launch
  * begins on the slabs the launch before it touched last; identical bits; 0: every launch forwards.  Read-only cg_sweep_alt_active: does the last CG set-up reverse its D^+),
  * dslash_sweep (measurement and tests; 1: every plain full-lattice application -- mul!, lqcd_bench_dslash -- that takes an eligible instance of the scalar-addressing kernel

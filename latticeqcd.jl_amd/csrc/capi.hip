@@ -3,6 +3,7 @@
 // rank = px + PX*(py + PY*(pz + PZ*pt)); one process (one context) per GPU.
 #include "lqcd_internal.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -65,6 +66,7 @@ lqcd_spinor_s* scratch_get(lqcd_ctx_s* c, int kind, int subset) {
             s->subset = subset;
             return s;
         }
+    if (c->tun.scratch_max > 0 && (int)c->scratch.size() >= c->tun.scratch_max) { set_error("scratch pool: all scratch_max work fields are in use"); return nullptr; }      // a capped pool does not grow (the callers fall back or fail as on an allocation failure)
     lqcd_spinor_s* s = nullptr;
     if (lqcd_spinor_create(c, &s, kind, subset) != LQCD_OK) return nullptr;
     s->in_use = true;
@@ -359,6 +361,9 @@ static int* param_ptr(lqcd_ctx_s* c, const char* key) {
     if (!strcmp(key, "cg_defer_x")) return &c->tun.cg_defer_x;
     if (!strcmp(key, "cg_rring")) return &c->tun.cg_rring;
     if (!strcmp(key, "cg_rring_active")) return &c->tun.cg_rring_active;
+    if (!strcmp(key, "cg_rring_mult")) return &c->tun.cg_rring_mult;
+    if (!strcmp(key, "cg_rring_depth_active")) return &c->tun.cg_rring_depth_active;
+    if (!strcmp(key, "scratch_max")) return &c->tun.scratch_max;
     if (!strcmp(key, "staggered_parity_solve")) return &c->tun.staggered_parity_solve;
     if (!strcmp(key, "halo_tuned_us0")) return &c->tun.halo_tuned_us[0];
     if (!strcmp(key, "halo_tuned_us1")) return &c->tun.halo_tuned_us[1];
@@ -410,6 +415,8 @@ extern "C" int lqcd_ctx_set_param(lqcd_ctx_t c, const char* key, int value) {
     if (!strcmp(key, "dslash_block")) ARGCHK(value == 64 || value == 128 || value == 256, "dslash_block must be 64, 128 or 256");
     if (!strcmp(key, "halo_stream_mode")) ARGCHK(value >= -1 && value <= 4, "halo_stream_mode must be -1 (timed once) or 0..4");
     if (!strcmp(key, "cg_rring")) ARGCHK(value == 0 || value == 2 || value == 4 || value == 8, "cg_rring must be 0 (off), 2, 4 or 8 (it divides the 8 iterations of a captured burst)");
+    if (!strcmp(key, "cg_rring_mult")) ARGCHK((value == 1 || value == 2 || value == 4) && std::max(c->tun.cg_rring, 1) * value <= RRING_MAX, "cg_rring_mult must be 1, 2 or 4 with cg_rring x cg_rring_mult <= 32");
+    if (!strcmp(key, "scratch_max")) ARGCHK(value >= 0, "scratch_max: 0 (no limit) or the number of work fields the scratch pool may hold");
     if (!strcmp(key, "bicg_fused")) ARGCHK(value != 3, "bicg_fused must be 0, 1, 2 or 4 (3, the grid-barrier form, was measured slower and removed)");
     if (!strcmp(key, "halo_inject_us")) ARGCHK(value >= 0 && value <= 100000, "halo_inject_us: 0..100000");
     if ((!strcmp(key, "lazy_links") || !strcmp(key, "lazy_merge")) && !value) LQCHK(links_flush_of(c));      // switching to eager calls: what is recorded runs now
@@ -417,6 +424,7 @@ extern "C" int lqcd_ctx_set_param(lqcd_ctx_t c, const char* key, int value) {
     // a key that changes while something is recorded runs the records first
     if (*p != value) LQCHK(links_flush_of(c));
     *p = value;
+    if (!strcmp(key, "cg_rring_mult")) c->tun.cg_rring_mult_set = 1;
     return LQCD_OK;
 }
 extern "C" int lqcd_ctx_get_param(lqcd_ctx_t c, const char* key, int* value) {

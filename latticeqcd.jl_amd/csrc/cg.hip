@@ -276,33 +276,55 @@ __global__ __launch_bounds__(UB) void cg_flush_ring(const double* __restrict__ s
         x[i] = xv;
     }
 }
-// ---- cg_fused = 3, the residual ring: D p by recurrence from D r; p and x brought up to date once per K iterations (tunable cg_rring = K = 2, 4, 8).
+// ---- cg_fused = 3, the residual ring: D p by recurrence from D r; p and x brought up to date once per K iterations (tunable cg_rring = K = 2, 4, 8; with the tunable
+// cg_rring_mult = M = 2, 4 the ring has K M <= 32 slots and everything below holds with K M in place of K -- the depth; cg_rring_active reports K, cg_rring_depth_active K M).
 // With s_k = D p_k and p_{k+1} = r_{k+1} + beta_k p_k:  s_{k+1} = D r_{k+1} + beta_k s_k.  The stencil is applied to the residual the D^+ before it has just written
 // (recurrence mode of the scalar-addressing kernel: s read at the centre, s = v + beta s stored in place), so p is needed only to accumulate x: the K residuals of a
 // batch stay in a ring of K slots (update-mode D^+ reads r_k from slot k % K and writes r_{k+1} to the next), alpha_k / beta_k go to S_AHIST / S_BHIST, and every K-th
 // iteration ONE streaming launch (cg_batch_px) forms x and p by the fma sequence of cg_update_xp; the D behind it is a plain D on the fresh p, which restarts the
 // recurrence (its rounding error lives for at most K - 1 steps).  Per site and iteration: 864 B (D, recurrence mode) + 864 B (D^+) + ((K + 4) 192 + 672 - 864) / K B
-// = 2208 / 2064 / 1992 B for K = 2 / 4 / 8, against the 2400 B of the two-buffer deferred-x form; 4 + 1 / K launches instead of 5.
+// = 2208 / 2064 / 1992 / 1944 / 1920 B for depth 2 / 4 / 8 / 16 / 32, against the 2400 B of the two-buffer deferred-x form; 4 + 1 / K launches instead of 5.  The batch
+// kernel alone: 192 (K + 4) / K = 288 / 240 / 216 B per site and iteration at depth 8 / 16 / 32; 192 of them are the one further read of each residual.
 // Where: cg_setup's gate (cg_rring_wanted) -- Wilson, r = 1, no clover term, one unpartitioned GPU without a communicator, the scalar-addressing kernel, beyond cg_small.
 // Costed and not built: (a) the batch folded into the D behind it -- the stencil would read the K residuals and p at every NEIGHBOUR as well (the new p is its
-// hop operand): 8 x (K + 1) more reads than the K + 4 streams it saves; (b) K that does not divide 8 -- a captured burst of 8 iterations bakes the slot roles in, the
-// replay must find the ring where it left it; (c) staggered, fp32 / mixed-precision, multi-shift, even-odd and partitioned solvers: the same recurrence applies, their
+// hop operand): 8 x (K + 1) more reads than the K + 4 streams it saves; (b) a depth that neither divides 8 nor is a multiple of it -- a captured burst bakes the slot
+// roles in, the replay must find the ring where it left it (cg_run captures max(8, K M) iterations); (c) staggered, fp32 / mixed-precision, multi-shift, even-odd and partitioned solvers: the same recurrence applies, their
 // kernels have no centre read separate from the store ("not done").
-struct CgSlots { const double2* r[8]; };      // slot of r_{b+j+1}, j = 0..7, b the first iteration of the batch (entries >= K unused); indexed by unrolled constants only
+struct CgSlots { const double2* r[RRING_MAX]; };      // slot of r_{b+j+1}, j = 0..depth-1, b the first iteration of the batch (entries >= depth unused); indexed by unrolled constants only
 // x += alpha_j p_j, p_{j+1} = r_{j+1} + beta_j p_j for the pending iterations j = 0 .. np - 1, oldest first (np = S_ITERS - S_BSTART, from the device).  fin = 0 (batch
-// boundary inside a window): np = K, writes x and p; a no-op once the solve is done.  fin = 1 (cg_flush_x: a converged solve, an exhausted one, the end of a window):
-// applies the np pending terms to x, whatever the done flag says, and forms no p nobody uses.
-template <bool NT>
+// boundary inside a window): np = DEPTH, writes x and p; a no-op once the solve is done.  fin = 1 (cg_flush_x: a converged solve, an exhausted one, the end of a window):
+// applies the np pending terms to x, whatever the done flag says, and forms no p nobody uses.  One instance per ring depth (8: cg_rring = 2, 4, 8 with cg_rring_mult = 1;
+// 16, 32), the loop over the pending iterations fully unrolled; one pass per element: x, p and the slots are read once, x and p written once.  At DEPTH 32 the full
+// batch (fin = 0, np = DEPTH) takes a loop without a test on np, so the 34 loads of an element are independent of every branch and the compiler issues them together
+// (164 VGPRs, three waves per SIMD); the fma sequence per element is the same on both paths.  Measured (profiles/r17_rring_depth_ab.log): that loop is +1.1 % on the
+// iteration at depth 32, nothing at 16 and -1.6 % at 8 -- so depths 8 and 16 keep the plain loop alone (20 / 22 VGPRs), and depth 8 is the kernel it always was.
+template <bool NT, int DEPTH>
 __global__ __launch_bounds__(UB) void cg_batch_px(const double* __restrict__ s, double2* __restrict__ x, double2* __restrict__ p, CgSlots sl, int fin, size_t n) {
     const int np = (int)(s[S_ITERS] - s[S_BSTART]);
-    if (np <= 0 || np > 8 || (!fin && s[S_DONE] != 0.0)) return;
-    double al[8], be[8];
+    if (np <= 0 || np > DEPTH || (!fin && s[S_DONE] != 0.0)) return;
+    double al[DEPTH], be[DEPTH];
 #pragma unroll
-    for (int j = 0; j < 8; j++) { al[j] = j < np ? s[S_AHIST + j] : 0.0; be[j] = j < np ? s[S_BHIST + j] : 0.0; }
+    for (int j = 0; j < DEPTH; j++) { al[j] = j < np ? s[S_AHIST + j] : 0.0; be[j] = j < np ? s[S_BHIST + j] : 0.0; }
+    if (DEPTH >= 32 && !fin && np == DEPTH) {
+        for (size_t i = (size_t)blockIdx.x * UB + threadIdx.x; i < n; i += (size_t)gridDim.x * UB) {
+            double2 xv = ldx<NT>(x + i), pv = ldx<NT>(p + i);
+            double2 rv[DEPTH];
+#pragma unroll
+            for (int j = 0; j < DEPTH; j++) rv[j] = ldx<NT>(sl.r[j] + i);
+#pragma unroll
+            for (int j = 0; j < DEPTH; j++) {
+                xv.x = fma(al[j], pv.x, xv.x); xv.y = fma(al[j], pv.y, xv.y);
+                pv.x = fma(be[j], pv.x, rv[j].x); pv.y = fma(be[j], pv.y, rv[j].y);
+            }
+            stx<NT>(x + i, xv);
+            stx<NT>(p + i, pv);
+        }
+        return;
+    }
     for (size_t i = (size_t)blockIdx.x * UB + threadIdx.x; i < n; i += (size_t)gridDim.x * UB) {
         double2 xv = ldx<NT>(x + i), pv = ldx<NT>(p + i);
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
+        for (int j = 0; j < DEPTH; j++) {
             if (j < np) {
                 xv.x = fma(al[j], pv.x, xv.x); xv.y = fma(al[j], pv.y, xv.y);
                 if (!fin || j < np - 1) {
@@ -435,12 +457,19 @@ static CgRing cg_ring_pending(const CgWork& w, int m) {      // the buffers of p
     for (int j = 0; j < 8; j++) ring.b[j] = j < m ? w.buf((w.k - m + j) % w.ring)->data : nullptr;
     return ring;
 }
+template <int DEPTH>
+static void cg_batch_launch_depth(lqcd_ctx_s* c, bool nt, dim3 g, dim3 b, lqcd_spinor_s* x, CgWork& w, const CgSlots& sl, int fin) {
+    if (nt) hipLaunchKernelGGL((cg_batch_px<true, DEPTH>), g, b, 0, c->stream, c->d_scal, x->data, w.p->data, sl, fin, x->elems);
+    else hipLaunchKernelGGL((cg_batch_px<false, DEPTH>), g, b, 0, c->stream, c->d_scal, x->data, w.p->data, sl, fin, x->elems);
+}
 static int cg_batch_launch(lqcd_ctx_s* c, lqcd_spinor_s* x, CgWork& w, int fin) {
     CgSlots sl;
-    for (int j = 0; j < 8; j++) sl.r[j] = j < w.rring ? w.slot((j + 1) % w.rring)->data : nullptr;
+    for (int j = 0; j < RRING_MAX; j++) sl.r[j] = j < w.rring ? w.slot((j + 1) % w.rring)->data : nullptr;
     const dim3 g(stream_grid(c, x->elems)), b(UB);
-    if (c->tun.nt_blas) hipLaunchKernelGGL(cg_batch_px<true>, g, b, 0, c->stream, c->d_scal, x->data, w.p->data, sl, fin, x->elems);
-    else hipLaunchKernelGGL(cg_batch_px<false>, g, b, 0, c->stream, c->d_scal, x->data, w.p->data, sl, fin, x->elems);
+    const bool nt = c->tun.nt_blas != 0;
+    if (w.rring <= 8) cg_batch_launch_depth<8>(c, nt, g, b, x, w, sl, fin);
+    else if (w.rring == 16) cg_batch_launch_depth<16>(c, nt, g, b, x, w, sl, fin);
+    else cg_batch_launch_depth<32>(c, nt, g, b, x, w, sl, fin);
     HIPCHK(hipGetLastError());
     return LQCD_OK;
 }
@@ -716,6 +745,15 @@ int cg_enqueue_iteration(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
     return LQCD_ERR_ARG;
 }
 
+// the ring depth multiplier for this solve: the tunable cg_rring_mult, as long as K M <= RRING_MAX (the largest admissible M below it otherwise).  A context that never set
+// the tunable keeps M = 1 in the launch-bound regime (<= 1024 stencil workgroups, where cg_small would apply): the deep ring was measured on lattices beyond it only.
+static int cg_rring_mult_wanted(lqcd_op_s* op, int K) {
+    lqcd_ctx_s* c = op->ctx;
+    int M = c->tun.cg_rring_mult;
+    if (!c->tun.cg_rring_mult_set && stencil_num_partials(c, op->kind, op->r, 2, 0, op_fused_clover(op)) <= 1024) M = 1;
+    while (M > 1 && K * M > RRING_MAX) M >>= 1;
+    return M;
+}
 // K - 2 more work vectors for a ring of K buffers (those already held are kept); K < 2 or a pool that cannot grow: none stay held, false
 static bool cg_more_get(lqcd_ctx_s* c, CgWork& w, int K) {
     bool ok = K >= 2;
@@ -726,13 +764,17 @@ static bool cg_more_get(lqcd_ctx_s* c, CgWork& w, int K) {
     if (!ok) for (lqcd_spinor_s*& f : w.more) { if (f) scratch_put(f); f = nullptr; }
     return ok;
 }
-// The one place the tunables pick the iteration form.  The small-lattice form first; then cg_fused = 3, the residual ring (its K does not depend on `graph`: 2, 4, 8
-// divide a captured burst) with its K - 2 extra vectors -- the forms below if the pool cannot grow; then the deferred x update; then by cg_fused.
+// The one place the tunables pick the iteration form.  The small-lattice form first; then cg_fused = 3, the residual ring (its depth K M does not depend on `graph`: cg_run
+// makes a captured burst a multiple of it) with its K M - 2 extra vectors -- M is halved while the pool cannot supply them, then the forms below; then the deferred x
+// update; then by cg_fused.
 static CgForm cg_choose_form(lqcd_op_s* op, CgWork& w) {
     lqcd_ctx_s* c = op->ctx;
     const int fused = c->tun.cg_fused;
     if (fused >= 2 && c->tun.cg_small && cg_small_ok(op, stencil_num_partials(c, op->kind, op->r, 2, 0, op_fused_clover(op)))) return CgForm::Small;
-    if (cg_more_get(c, w, cg_rring_wanted(op, w))) return CgForm::RRing;
+    if (const int K = cg_rring_wanted(op, w)) {
+        for (int M = cg_rring_mult_wanted(op, K); M >= 1; M >>= 1)
+            if (cg_more_get(c, w, K * M)) { w.rring = K * M; w.rring_k = K; return CgForm::RRing; }
+    }
     if (fused >= 2 && c->tun.cg_defer_x) return CgForm::DeferX;
     return fused >= 2 ? CgForm::Fused : fused ? CgForm::NormFused : CgForm::Reference;
 }
@@ -761,9 +803,10 @@ int cg_setup(lqcd_op_s* op, lqcd_spinor_s* x, lqcd_spinor_s* b, CgWork& w, doubl
     HIPCHK(hipMemcpyAsync(c->d_scal + S_RR, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     w.k = 0; w.p_packed = false; w.flushed = false;
-    w.form = cg_choose_form(op, w);
-    w.rring = w.form == CgForm::RRing ? c->tun.cg_rring : 0;
-    c->tun.cg_rring_active = w.rring;
+    w.rring = w.rring_k = 0;
+    w.form = cg_choose_form(op, w);      // (RRing: sets the depth w.rring = K M and w.rring_k = K)
+    c->tun.cg_rring_active = w.rring_k;
+    c->tun.cg_rring_depth_active = w.rring;
     // the alternating sweep: the forms whose D^+ is a launch of the temporal-gauge instance (away from the seam it loads no time-like link, so no streaming hint sits on the
     // first use of one when t runs backwards).  Fixed here like the form: no iteration reads the tunable.
     w.sweep_alt = c->tun.cg_sweep_alt != 0 && w.tgauge && (w.form == CgForm::RRing || w.form == CgForm::Fused || w.form == CgForm::DeferX);
@@ -797,7 +840,7 @@ int cg_run(lqcd_op_s* op, lqcd_spinor_s* x, lqcd_spinor_s* b, double eps, int ma
     }
     if (st == LQCD_OK && !one_launch) st = cg_setup(op, x, b, w, fixed ? -1.0 : eps, &rr);
     if (st == LQCD_OK && !one_launch && !fixed && rr < eps) converged = true;
-    const int check_every = 8;
+    int check_every = 8;
     // Launch-bound lattices (the cg_small regime: <= 1024 stencil workgroups, an iteration is three ~5 us launches): every readback of the
     // scalar block is a host synchronisation worth about two iterations, an iteration enqueued behind the converging one only three no-op
     // launches.  There the burst length follows the observed convergence rate -- enough iterations to reach eps by the rate of the last
@@ -808,6 +851,9 @@ int cg_run(lqcd_op_s* op, lqcd_spinor_s* x, lqcd_spinor_s* b, double eps, int ma
     // tunable "graph": a burst of check_every iterations is captured once into a hipGraph and replayed -- one launch per
     // burst instead of 5 per iteration.  Pays on launch-bound (small) lattices; single-stream (unpartitioned) contexts only.
     const bool use_graph = c->tun.graph != 0 && !any_partitioned(c) && !(c->has_comm && c->peer.on);      // (the peer-mapped reductions carry a sequence number per launch)
+    // residual ring: a replayed burst bakes the slot roles in, so it must leave the ring where it found it -- the captured burst is the multiple of the depth K M at or
+    // above 8 (8 for K M = 2, 4, 8; 16; 32).  The surplus iterations behind the converging one are no-ops (done flag): iterate and count do not depend on the burst length.
+    if (use_graph && w.form == CgForm::RRing && w.rring > 0) check_every = (check_every + w.rring - 1) / w.rring * w.rring;
     hipGraph_t graph = nullptr;
     hipGraphExec_t gexec = nullptr;
     while (st == LQCD_OK && !one_launch && !converged && it < maxiter) {

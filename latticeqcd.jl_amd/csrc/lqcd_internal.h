@@ -325,8 +325,11 @@ __device__ inline double shfl_tree_sum(double s) {      // lane 0 holds the sum 
 // slots of the device scalar block d_scal used by the solvers
 enum { S_RED0 = 0, S_RR = 8, S_PQ = 9, S_ALPHA = 10, S_BETA = 11, S_DONE = 12, S_ITERS = 13, S_EPS = 14, S_RRNEW = 15, S_XDONE = 16, S_RROLD = 17, S_APREV = 18,
        S_BSTART = 19,       // cg_fused = 3: the value of S_ITERS at the start of the batch whose x / p update is pending (S_ITERS - S_BSTART iterations are)
-       S_AHIST = 64,        // S_AHIST .. +7: the step lengths of the search directions whose x update is still pending (cg_defer_x >= 3: ring of p buffers; cg_fused = 3: the batch)
-       S_BHIST = 72 };      // S_BHIST .. +7: cg_fused = 3, the beta of the pending iterations (the host never reads either history)
+       S_AHIST = 64,        // S_AHIST .. +31: the step lengths of the search directions whose x update is still pending (cg_defer_x >= 3: ring of p buffers, 8 entries; cg_fused = 3: the batch, RRING_MAX)
+       S_BHIST = 96,        // S_BHIST .. +31: cg_fused = 3, the beta of the pending iterations (the host never reads either history)
+       S_HIST_END = 128 };
+constexpr int RRING_MAX = 32;      // cg_fused = 3: the deepest residual ring (cg_rring x cg_rring_mult slots); a power of two, the histories are indexed modulo it
+static_assert(S_BHIST - S_AHIST == RRING_MAX && S_HIST_END - S_BHIST == RRING_MAX && (RRING_MAX & (RRING_MAX - 1)) == 0, "the CG histories hold RRING_MAX entries each");
 // BiCGStab block (complex scalars are two consecutive doubles; B_TS..B_TT and B_RR..B_RHO1 are filled by one 3-value reduction)
 enum { B_RHO = 24, B_R0V = 26, B_VV = 28, B_ALPHA = 29, B_SS = 31, B_TS = 32, B_TT = 34, B_OMEGA = 35, B_RR = 37, B_RHO1 = 38, B_BETA = 40,
        B_DONE = 42, B_ITERS = 43, B_EPS = 44, B_HALF = 45, B_RES = 46, B_RHOB = 47, B_TS5 = 49, B_UNSURE = 54, B_XDONE = 55, B_END = 56 };   // B_TS5: <t, s>, |t|^2, <r0, t> of the merged chain (bicg_fused = 4), one 5-value reduction;      // B_R0V..B_VV, B_TS..B_TT and B_RR..B_RHO1 are filled by one
@@ -351,13 +354,13 @@ __device__ inline void cg_scalar_step(double* s, int op) {
         if (op == 9) s[S_BSTART] = s[S_ITERS];
         const double al = s[S_RR] / s[S_PQ];
         s[S_ALPHA] = al;
-        s[S_AHIST + ((int)(s[S_ITERS] - s[S_BSTART]) & 7)] = al;
+        s[S_AHIST + ((int)(s[S_ITERS] - s[S_BSTART]) & (RRING_MAX - 1))] = al;
     } else if (op == 8) {      // op 2 + beta into the history
         if (s[S_DONE] != 0.0) return;
         const double rrn = s[S_RRNEW];
         const double be = rrn / s[S_RR];
         s[S_BETA] = be;
-        s[S_BHIST + ((int)(s[S_ITERS] - s[S_BSTART]) & 7)] = be;
+        s[S_BHIST + ((int)(s[S_ITERS] - s[S_BSTART]) & (RRING_MAX - 1))] = be;
         s[S_RR] = rrn;
         s[S_ITERS] += 1.0;
         if (rrn < s[S_EPS]) s[S_DONE] = 1.0;
@@ -478,6 +481,11 @@ struct Tunables {
                               // the scalar-addressing Wilson kernel runs on one unpartitioned GPU, D p by recurrence from D r and p, x updated once per cg_rring iterations
     int cg_rring = 8;         // cg_fused = 3: K = 2, 4 or 8 (default) residual slots (p and x are brought up to date every K-th iteration; K divides the 8 iterations of a captured burst); 0: form off
     int cg_rring_active = 0;  // read-only: the K in use by the last CG set up through cg_setup, 0 if the form did not apply
+    int cg_rring_mult = 4;    // cg_fused = 3: M = 1, 2 or 4 (default; 1 in the launch-bound regime unless set, cg.hip cg_rring_mult_wanted), K M <= RRING_MAX: the ring has K M slots, the batch kernel and the plain D that restarts the recurrence run every
+                              // K M iterations (K M - 2 more work vectors; a pool that cannot grow halves M); a captured burst is K M iterations long
+    int scratch_max = 0;      // > 0: the scratch pool of work fields holds at most that many (a memory budget; solvers that want more fall back or fail as on an allocation failure)
+    int cg_rring_mult_set = 0;          // (internal) lqcd_ctx_set_param has been given cg_rring_mult: it holds at every volume (cg.hip cg_rring_mult_wanted)
+    int cg_rring_depth_active = 0;      // read-only: the K M in use by the last CG set up through cg_setup, 0 if the form did not apply
     int graph = 0;            // capture solver iterations in a hipGraph
     int persist_per_cu = 2;   // variant 3: resident workgroups per CU
     int dslash_pipe = 2;      // Wilson r = 1, variant 1, lattices whose z-planes are whole chunks: 1 = the persistent, software-pipelined form of the
@@ -970,7 +978,8 @@ struct lqcd_op_s {
 namespace lqcd {
 
 constexpr int MAX_PARTIAL_BLOCKS = 4096;
-constexpr int SCAL_DOUBLES = 96;
+constexpr int SCAL_DOUBLES = 144;     // the solvers' slots (.. S_HIST_END) + the 9 staging doubles at the end (blas.hip, fields.hip)
+static_assert(S_HIST_END + 9 <= SCAL_DOUBLES, "d_scal: the CG histories must end below the staging doubles");
 
 void set_error(const std::string& msg);
 int hip_fail(hipError_t e, const char* what, const char* file, int line);

@@ -30,10 +30,12 @@ struct CgWork {
     CgForm form = CgForm::Unset;      // fixed at cg_setup: the tunables may change while a session is open
     int k = 0;          // iterations enqueued so far (parity selects the p buffer when the x update is deferred: p_k lives in p for even k, in q for odd k)
     int ring = 2;       // DeferX: search-direction buffers in rotation (2: p, q; K > 2: p, q, more[0..K-3]; p_k lives in buffer k % K), fixed at cg_setup
-    lqcd_spinor_s* more[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    lqcd_spinor_s* more[RRING_MAX - 2] = {};      // (the DeferX ring takes at most 6 of them)
     lqcd_spinor_s* buf(int j) const { return j == 0 ? p : j == 1 ? q : more[j - 2]; }
-    // RRing (cg_fused = 3, cg.hip "residual ring"): r_k lives in slot k % rring (slots: r, q, more[0..rring-3]), p in p, s = D p in tmp
+    // RRing (cg_fused = 3, cg.hip "residual ring"): r_k lives in slot k % rring (slots: r, q, more[0..rring-3]), p in p, s = D p in tmp; rring = K M slots
+    // (tunables cg_rring = K, cg_rring_mult = M; M halved by cg_choose_form while the pool cannot supply rring - 2 more vectors)
     int rring = 0;
+    int rring_k = 0;    // the K of that depth (what cg_rring_active reports)
     bool flushed = false;    // RRing: the pending x terms have been applied (cg_flush_x); the window is over
     lqcd_spinor_s* slot(int j) const { return j == 0 ? r : j == 1 ? q : more[j - 2]; }
     // temporal gauge (decided once in cg_setup): x, r and the search directions are G times the caller's vectors and every stencil call of the iteration reads
