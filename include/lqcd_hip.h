@@ -405,6 +405,19 @@ int lqcd_gauge_exp_update(lqcd_gauge_t U, double dt, lqcd_gauge_t P);    /* U_up
 int lqcd_gauge_reunitarize(lqcd_gauge_t U);                              /* no reference counterpart: every link back onto SU(3) (Gram-Schmidt rows 0,1; row 2 = conj(row0 x row1)); once per trajectory keeps the 12-real Dslash alive under per-direction callers */
 int lqcd_momentum_gaussian(lqcd_gauge_t P, uint64_t seed);               /* gauss_distribution!(p) (src/md/standardMD.jl:86); keyed by GLOBAL site */
 int lqcd_momentum_action(lqcd_gauge_t P, double* K);                     /* p.p/2 (standardHMC.jl:49) */
+/* The plaquette + rectangle action (the reference's GaugeAction with couplingcoeff on [plaqloops, rectloops], examples/param_symanzik_improved_hb.jl):
+ *   S_g = -(1/3) [ beta_plaq sum_plaq Re tr U_p + beta_rect sum_rect Re tr U_r ], 6 V plaquettes and 12 V rectangles (1x2 and 2x1, every plane, every corner);
+ *   Luscher-Weisz beta_plaq = 5 beta / 3, beta_rect = -beta / 12; Iwasaki / DBW2 beta_plaq = (1 - 8 c1) beta, beta_rect = c1 beta, c1 = -0.331 / -1.4088;
+ *   G_mu(n) = -(1/6) U_mu(n) [ beta_plaq (six plaquette staples) + beta_rect (eighteen rectangle staples) ], a force field in the convention above.
+ * Single domain: a partitioned lattice or an in-process PE grid is refused with LQCD_ERR_UNSUPPORTED (the rectangles need a halo of depth 2).  An extent of 2 is
+ * computed (a 2-long side closes on itself through the periodic wrap).  beta_rect == 0.0 hands over to the plaquette entries above, bit for bit.  LQCD_ERR_ARG: null
+ * pointers, fields of different contexts, out == U, a direction outside 0..3; a refused call writes nothing. */
+int lqcd_gauge_rectangle(lqcd_gauge_t U, double* rect);                  /* mean of Re tr U_r / 3 over the 12 V rectangles: 1 on a cold field, normalised like lqcd_gauge_plaquette */
+int lqcd_gauge_action_improved(lqcd_gauge_t U, double beta_plaq, double beta_rect, double* Sg);
+int lqcd_gauge_force_improved(lqcd_gauge_t out, lqcd_gauge_t U, double beta_plaq, double beta_rect);
+int lqcd_momentum_add_gauge_force_improved(lqcd_gauge_t P, double factor, lqcd_gauge_t U, double beta_plaq, double beta_rect); /* P += factor TA(G), G never stored; P as for lqcd_momentum_add_gauge_force */
+int lqcd_link_staple_improved(lqcd_gauge_t out, int mu_out, lqcd_gauge_t U, int mu, double beta_plaq, double beta_rect); /* calc_dSdUmu! for this action: (beta_plaq/2) (plaquette staples) +
+                                                                          * (beta_rect/2) (rectangle staples) of direction mu, lqcd_link_staple's normalisation; eager (never recorded) */
 
 /* Single-direction forms: the reference's unchanged callers hold its Vector of link fields one direction at a time -- U[mu], p[mu]
  * and temporary link fields (src/md/AbstractMD.jl:78-135).  A "link field" here is (gauge-shaped field, direction slot 0..3); nothing

@@ -41,7 +41,7 @@ import LatticeDiracOperators: Dirac_operator, DdagD_operator, FermiAction, Initi
 export Initialize_HIPGaugefields, HIPLattice, HIPLink, HIPTALink, HIPFermion, HIPDirac, HIPFermiAction, reunitarize!, activate!, deactivate!,
     HIPGradientflow, flow_observables, energy_density, topological_charge, gradient_flow_measure, HIPHeatbath, heatbath_measure,
     wilson_loops, calc_Wilson_loop, meson_correlators, pion_correlator, Pion_correlator_measurement, measure,
-    hop_multi!, mul_multi!, solve_DinvX_multi!
+    hop_multi!, mul_multi!, solve_DinvX_multi!, calculate_Rectangle, gauge_force_improved!
 
 const LIB = get(ENV, "LQCD_HIP_LIB", joinpath(@__DIR__, "..", "latticeqcd.jl_amd", "csrc", "liblqcd_hip.so"))
 
@@ -442,20 +442,52 @@ end
 # get_temp and unused! are the PACKAGE's own: GaugeAction(U::Vector{<:AbstractGaugefields{NC,Dim}}) builds a GaugeAction{4,HIPLink}
 # whose temporaries are similar(U[1]) (above).  Specialised here are the two generics that do arithmetic.  The coupling is read from the
 # package's bookkeeping: dataset[i].β is the coefficient push! stored (β/2 for the plaquette and its adjoint together).
-function beta_inp(ga::GaugeAction{4,HIPLink})
-    all(d -> length(d.closedloops) == 12, ga.dataset) ||
-        error("the HIP staple kernel implements the plaquette action (make_loops_fromname(\"plaquette\") and its adjoint, universe.jl:92-93)")
-    return sum(d.β for d in ga.dataset)
+# A second push!(gauge_action, β_rect/2, rectloop ∪ rectloop') with make_loops_fromname("rectangular") gives the plaquette + rectangle actions of the
+# reference's couplingcoeff / coupling_loops (examples/param_symanzik_improved_hb.jl: [β*5/3, -β/12] on [plaqloops, rectloops]).  The two sets are told
+# apart by their size: 6 plaquettes or 12 rectangles (1x2 and 2x1 of every plane), each with its adjoint.
+function betas_inp(ga::GaugeAction{4,HIPLink})
+    bp, br = 0.0, 0.0
+    for d in ga.dataset
+        n = length(d.closedloops)
+        if n == 12
+            bp += d.β
+        elseif n == 24
+            br += d.β
+        else
+            error("the HIP staple kernels implement the plaquette and the rectangle loops (make_loops_fromname(\"plaquette\" | \"rectangular\"), each with its adjoint)")
+        end
+    end
+    return bp, br
 end
-# calc_dSdUμ!(dSdUμ, gauge_action, μ, U) (AbstractMD.jl:108): β_inp * (sum of the staples of U[μ])
-calc_dSdUμ!(dSdUμ::HIPLink, ga::GaugeAction{4,HIPLink}, μ::Integer, U::Vector{HIPLink}) =
+beta_inp(ga::GaugeAction{4,HIPLink}) = betas_inp(ga)[1]
+beta_rect_inp(ga::GaugeAction{4,HIPLink}) = betas_inp(ga)[2]
+# calc_dSdUμ!(dSdUμ, gauge_action, μ, U) (AbstractMD.jl:108): β_inp * (sum of the staples of U[μ]); with rectangles in the action link_staple_improved!
+calc_dSdUμ!(dSdUμ::HIPLink, ga::GaugeAction{4,HIPLink}, μ::Integer, U::Vector{HIPLink}) = beta_rect_inp(ga) != 0 ? link_staple_improved!(dSdUμ, ga, μ, U) :
     check(ccall((:lqcd_link_staple, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Float64), hof(dSdUμ), slotof(dSdUμ), whole(U).h, μ - 1, 2 * beta_inp(ga)))
+# β_inp * (plaquette staples) + β_rect_inp * (rectangle staples) of U[μ]; run at once, the mul! / Traceless_antihermitian_add! behind it are the generic ones
+link_staple_improved!(dSdUμ::HIPLink, ga::GaugeAction{4,HIPLink}, μ::Integer, U::Vector{HIPLink}) =
+    check(ccall((:lqcd_link_staple_improved, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Float64, Float64),
+                hof(dSdUμ), slotof(dSdUμ), whole(U).h, μ - 1, 2 * beta_inp(ga), 2 * beta_rect_inp(ga)))
 # evaluate_GaugeAction(gauge_action, U) (standardHMC.jl:50,60; S_g = -that / NC): lqcd_gauge_action returns S_g itself
 function evaluate_GaugeAction(ga::GaugeAction{4,HIPLink}, U::Vector{HIPLink})
     s = Ref{Float64}(0)
-    check(ccall((:lqcd_gauge_action, LIB), Cint, (Ptr{Cvoid}, Float64, Ref{Float64}), whole(U).h, 2 * beta_inp(ga), s))
+    bp, br = betas_inp(ga)
+    if br != 0
+        check(ccall((:lqcd_gauge_action_improved, LIB), Cint, (Ptr{Cvoid}, Float64, Float64, Ref{Float64}), whole(U).h, 2 * bp, 2 * br, s))
+    else
+        check(ccall((:lqcd_gauge_action, LIB), Cint, (Ptr{Cvoid}, Float64, Ref{Float64}), whole(U).h, 2 * bp, s))
+    end
     return -3 * s[]
 end
+# mean of Re tr U_r / NC over the 12 V rectangles, normalised like calculate_Plaquette
+function calculate_Rectangle(U::Vector{HIPLink})
+    r = Ref{Float64}(0)
+    check(ccall((:lqcd_gauge_rectangle, LIB), Cint, (Ptr{Cvoid}, Ref{Float64}), whole(U).h, r))
+    return r[]
+end
+# the force field G = -(1/6) U [β_plaq (plaquette staples) + β_rect (rectangle staples)] of this action, all four directions
+gauge_force_improved!(G::Vector{HIPLink}, U::Vector{HIPLink}, β_plaq, β_rect) =
+    check(ccall((:lqcd_gauge_force_improved, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64), whole(G).h, whole(U).h, β_plaq, β_rect))
 
 # ------------------------------------------------------------------ fermion fields
 mutable struct HIPFermion <: AbstractFermionfields_4D{3}
@@ -783,7 +815,10 @@ measure(m::Pion_correlator_measurement, U::Vector{HIPLink}) = pion_correlator(m.
 # P_update!(U::Vector{HIPLink}, p, ϵ, md) / U_update! method to skip the per-direction temporaries)
 P_update_fused!(U::Vector{HIPLink}, p::Vector{HIPTALink}, factor, β) =      # p += factor * TA(-(β/6) U * staples), the force field is never stored
     check(ccall((:lqcd_momentum_add_gauge_force, LIB), Cint, (Ptr{Cvoid}, Float64, Ptr{Cvoid}, Float64), whole(p).h, factor, whole(U).h, β))
-U_update_fused!(U::Vector{HIPLink}, p::Vector{HIPTALink}, dt) =             # U <- exp(dt p) U (reprojected onto SU(3): tunable md_reunitarize)
+P_update_fused!(U::Vector{HIPLink}, p::Vector{HIPTALink}, factor, β_plaq, β_rect) =      # the same for the plaquette + rectangle action
+    check(ccall((:lqcd_momentum_add_gauge_force_improved, LIB), Cint, (Ptr{Cvoid}, Float64, Ptr{Cvoid}, Float64, Float64), whole(p).h, factor, whole(U).h, β_plaq, β_rect))
+P_update_fused!(U::Vector{HIPLink}, p::Vector{HIPTALink}, factor, ga::GaugeAction{4,HIPLink}) = P_update_fused!(U, p, factor, 2 * beta_inp(ga), 2 * beta_rect_inp(ga))
+U_update_fused!(U::Vector{HIPLink}, p::Vector{HIPTALink}, dt) =            # U <- exp(dt p) U (reprojected onto SU(3): tunable md_reunitarize)
     check(ccall((:lqcd_gauge_exp_update, LIB), Cint, (Ptr{Cvoid}, Float64, Ptr{Cvoid}), whole(U).h, dt, whole(p).h))
 momentum_add_ta_fused!(p::Vector{HIPTALink}, factor, G::Vector{HIPLink}) =  # p += factor * TA(G), all four directions
     check(ccall((:lqcd_momentum_add_ta, LIB), Cint, (Ptr{Cvoid}, Float64, Ptr{Cvoid}), whole(p).h, factor, whole(G).h))

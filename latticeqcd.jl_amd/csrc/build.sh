@@ -20,7 +20,7 @@ if [ -n "$ALT" ]; then
     pids+=($!)
   fi
 fi
-for f in stencil stencil_pair32 cg_persist fields blas apply comm cg bicgstab bicgstab_eo multishift actions rational bench_api mdom capi force mixed md staple links stout clover domainwall flow heatbath wilsonloop meson stencil_mrhs bicgstab_eo_mrhs; do
+for f in stencil stencil_pair32 cg_persist fields blas apply comm cg bicgstab bicgstab_eo multishift actions rational bench_api mdom capi force mixed md staple links stout clover domainwall flow heatbath wilsonloop meson stencil_mrhs bicgstab_eo_mrhs rectangle; do
   if [ ! -f $BDIR/$f.o ] || [ $f.hip -nt $BDIR/$f.o ] || [ lqcd_internal.h -nt $BDIR/$f.o ] || [ ops_internal.h -nt $BDIR/$f.o ] || [ stencil_common.h -nt $BDIR/$f.o ] || [ gauge_staple.h -nt $BDIR/$f.o ] || [ ../../include/lqcd_hip.h -nt $BDIR/$f.o ] || [ build.sh -nt $BDIR/$f.o ]; then
     # the compiler's per-kernel resource remarks (registers, scratch, occupancy) are kept beside the object: scripts/resource_usage.py, tests/test_kernel_resources.py
     ( set +e; hipcc $FLAGS -Rpass-analysis=kernel-resource-usage -c $f.hip -o $BDIR/$f.o 2> $BDIR/$f.remarks; rc=$?; if [ $rc != 0 ]; then grep -v "remark:" $BDIR/$f.remarks >&2 || true; else grep -A3 "warning:" $BDIR/$f.remarks >&2 || true; fi; exit $rc ) &
@@ -34,5 +34,5 @@ fi
 fail=0
 for p in "${pids[@]}"; do wait $p || fail=1; done
 [ $fail = 0 ] || { echo "compilation failed" >&2; exit 1; }
-hipcc --offload-arch=$ARCH -shared -fPIC -o $OUT $BDIR/stencil.o $BDIR/stencil32.o ${ALT:+$BDIR/stencil_alt.o} $BDIR/stencil_pair32.o $BDIR/cg_persist.o $BDIR/fields.o $BDIR/blas.o $BDIR/apply.o $BDIR/comm.o $BDIR/cg.o $BDIR/bicgstab.o $BDIR/bicgstab_eo.o $BDIR/multishift.o $BDIR/actions.o $BDIR/rational.o $BDIR/bench_api.o $BDIR/mdom.o $BDIR/capi.o $BDIR/force.o $BDIR/mixed.o $BDIR/md.o $BDIR/staple.o $BDIR/links.o $BDIR/stout.o $BDIR/clover.o $BDIR/domainwall.o $BDIR/flow.o $BDIR/heatbath.o $BDIR/wilsonloop.o $BDIR/meson.o $BDIR/stencil_mrhs.o $BDIR/bicgstab_eo_mrhs.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+hipcc --offload-arch=$ARCH -shared -fPIC -o $OUT $BDIR/stencil.o $BDIR/stencil32.o ${ALT:+$BDIR/stencil_alt.o} $BDIR/stencil_pair32.o $BDIR/cg_persist.o $BDIR/fields.o $BDIR/blas.o $BDIR/apply.o $BDIR/comm.o $BDIR/cg.o $BDIR/bicgstab.o $BDIR/bicgstab_eo.o $BDIR/multishift.o $BDIR/actions.o $BDIR/rational.o $BDIR/bench_api.o $BDIR/mdom.o $BDIR/capi.o $BDIR/force.o $BDIR/mixed.o $BDIR/md.o $BDIR/staple.o $BDIR/links.o $BDIR/stout.o $BDIR/clover.o $BDIR/domainwall.o $BDIR/flow.o $BDIR/heatbath.o $BDIR/wilsonloop.o $BDIR/meson.o $BDIR/stencil_mrhs.o $BDIR/bicgstab_eo_mrhs.o $BDIR/rectangle.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 echo "built $(pwd)/$OUT"

@@ -7,7 +7,7 @@
 //
 // Conventions (the packages that own these generics are not vendored; these are fixed by dH/dtau = 0 and tested as such):
 //   momenta P_mu(n): traceless anti-Hermitian 3x3 matrices in a gauge-shaped field, K = -sum tr P^2 (= p.p/2 for P = i p_a T_a);
-//   dU/dtau = P U (U <- exp(dt P) U);   S_g = -(beta/3) sum_plaq Re tr U_p;
+//   dU/dtau = P U (U <- exp(dt P) U);   S_g = -(beta/3) sum_plaq Re tr U_p   (with rectangles: -(1/3) [beta_plaq sum_plaq + beta_rect sum_rect], rectangle.hip);
 //   every force field G obeys dS/d eps [U -> exp(i eps T) U] = -2 Im tr(T G), hence dP/dtau = TA(G) = (G - G^+)/2 - tr(.)/3.
 #include "lqcd_internal.h"
 #include "gauge_staple.h"

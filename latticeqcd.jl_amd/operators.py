@@ -1184,30 +1184,43 @@ def back_prop(dSdU, nn, Uout_multi, U):
 
 
 class GaugeAction:
-    """GaugeAction(U) + push!(gauge_action, beta/2, plaqloop) (universe.jl:88-96): the plaquette action of the reference's runs.
+    """GaugeAction(U) + push!(gauge_action, coeff, loops) (universe.jl:88-96): the plaquette action of the reference's runs (beta/2 on plaqloop and its
+    adjoint), and the plaquette + rectangle actions of its couplingcoeff / coupling_loops parameters (examples/param_symanzik_improved_hb.jl:
+    [beta*5/3, -beta/12] on [plaqloops, rectloops]) -- a second push_ with the rectangle set.
     Owns the temporary link fields P_update! / U_update! borrow (get_temporary_gaugefields, AbstractMD.jl:79,101,122)."""
 
     def __init__(self, U):
         self.lattice = U.lattice
         self.beta_inp = 0.0
+        self.beta_rect_inp = 0.0
         self._temps = Temporalfields(U.lattice)
 
-    def push_(self, beta_inp, loops):
-        if loops != make_loops_fromname("plaquette") + make_loops_fromname("plaquette", adjoint=True):
-            raise LQCDError(_l.ERR_UNSUPPORTED, "only the plaquette loop and its adjoint (universe.jl:92-95) are supported on the HIP path")
-        self.beta_inp += float(beta_inp)
+    def push_(self, coeff, loops):
+        if loops == make_loops_fromname("plaquette") + make_loops_fromname("plaquette", adjoint=True):
+            self.beta_inp += float(coeff)
+        elif loops == make_loops_fromname("rectangular") + make_loops_fromname("rectangular", adjoint=True):
+            self.beta_rect_inp += float(coeff)
+        else:
+            raise LQCDError(_l.ERR_UNSUPPORTED, "the plaquette loops and the rectangular loops, each with its adjoint (universe.jl:92-95), are supported on the HIP path")
         return self
 
     @property
     def beta(self):            # beta/2 on the loop and on its adjoint
         return 2.0 * self.beta_inp
 
+    @property
+    def beta_rect(self):       # the coefficient of the rectangles, pushed the same way
+        return 2.0 * self.beta_rect_inp
+
 
 def make_loops_fromname(name, Dim=4, adjoint=False):
-    """make_loops_fromname("plaquette", Dim=Dim) (universe.jl:92); append!(plaqloop, plaqloop') adds the adjoint loops."""
-    if name != "plaquette":
-        raise LQCDError(_l.ERR_UNSUPPORTED, f"loop {name} is not supported")
-    return [("plaquette-adjoint" if adjoint else "plaquette", mu, nu) for mu in range(1, Dim + 1) for nu in range(mu + 1, Dim + 1)]
+    """make_loops_fromname("plaquette", Dim=Dim) (universe.jl:92); append!(plaqloop, plaqloop') adds the adjoint loops.  "rectangular": the 1x2 and 2x1
+    rectangles of every plane, (name, long direction, short direction)."""
+    if name == "plaquette":
+        return [("plaquette-adjoint" if adjoint else "plaquette", mu, nu) for mu in range(1, Dim + 1) for nu in range(mu + 1, Dim + 1)]
+    if name == "rectangular":
+        return [("rectangular-adjoint" if adjoint else "rectangular", mu, nu) for mu in range(1, Dim + 1) for nu in range(1, Dim + 1) if mu != nu]
+    raise LQCDError(_l.ERR_UNSUPPORTED, f"loop {name} is not supported")
 
 
 class Temporalfields:
@@ -1265,25 +1278,49 @@ def exptU_(expU, t, p_mu, temps=None):
 
 def calc_dSdUmu_(dSdUmu, gauge_action, mu, U):
     """calc_dSdUμ!(dSdUμ, gauge_action, μ, U) (AbstractMD.jl:108): beta_inp * (sum of the staples of U[μ]), μ = 1..4 (first call of the P_update!
-    triple: recorded by the library)."""
+    triple: recorded by the library).  With rectangles in the action: beta_inp * (plaquette staples) + beta_rect_inp * (rectangle staples), run at once."""
+    beta_rect = getattr(gauge_action, "beta_rect", 0.0)      # any object with a .beta serves as a plaquette action
+    if beta_rect != 0.0:
+        check(_l.lib().lqcd_link_staple_improved(dSdUmu.field._h, dSdUmu.slot, U._h, int(mu) - 1, C.c_double(gauge_action.beta), C.c_double(beta_rect)))
+        return dSdUmu
     check(_l.lib().lqcd_link_staple(dSdUmu.field._h, dSdUmu.slot, U._h, int(mu) - 1, C.c_double(gauge_action.beta)))
     return dSdUmu
 
 
-def evaluate_GaugeAction(a, b):
+def _betas(beta, beta_rect):
+    """(beta_plaq, beta_rect) from a GaugeAction or from numbers"""
+    if isinstance(beta, GaugeAction):
+        return beta.beta, beta.beta_rect
+    return float(beta), float(beta_rect)
+
+
+def evaluate_GaugeAction(a, b, beta_rect=0.0):
     """Reference form evaluate_GaugeAction(gauge_action, U) (standardHMC.jl:50; S_g = -that/NC), and the direct
-    evaluate_GaugeAction(U, beta) = S_g = -(beta/3) sum_plaq Re tr U_p."""
+    evaluate_GaugeAction(U, beta, beta_rect=0.0) = S_g = -(1/3) [beta sum_plaq Re tr U_p + beta_rect sum_rect Re tr U_r]."""
     s = C.c_double(0)
-    if isinstance(a, GaugeAction):
-        check(_l.lib().lqcd_gauge_action(b._h, C.c_double(a.beta), C.byref(s)))
-        return -3.0 * s.value
-    check(_l.lib().lqcd_gauge_action(a._h, C.c_double(b), C.byref(s)))
-    return s.value
+    U, (bp, br) = (b, _betas(a, 0.0)) if isinstance(a, GaugeAction) else (a, _betas(b, beta_rect))
+    if br != 0.0:
+        check(_l.lib().lqcd_gauge_action_improved(U._h, C.c_double(bp), C.c_double(br), C.byref(s)))
+    else:
+        check(_l.lib().lqcd_gauge_action(U._h, C.c_double(bp), C.byref(s)))
+    return -3.0 * s.value if isinstance(a, GaugeAction) else s.value
 
 
-def gauge_force_(G, U, beta):
-    """calc_dSdUmu! followed by mul!(temp, U, dSdUmu) (AbstractMD.jl:108-109): G = -(beta/6) U * staples."""
-    check(_l.lib().lqcd_gauge_force(G._h, U._h, C.c_double(beta)))
+def calculate_Rectangle(U):
+    """Mean of Re tr U_r / NC over the 12 V rectangles (1x2 and 2x1, every plane, every corner), normalised like calculate_Plaquette."""
+    r = C.c_double(0)
+    check(_l.lib().lqcd_gauge_rectangle(U._h, C.byref(r)))
+    return r.value
+
+
+def gauge_force_(G, U, beta, beta_rect=0.0):
+    """calc_dSdUmu! followed by mul!(temp, U, dSdUmu) (AbstractMD.jl:108-109): G = -(beta/6) U * staples; beta may be a GaugeAction, and with
+    rectangles G = -(1/6) U [beta (plaquette staples) + beta_rect (rectangle staples)]."""
+    bp, br = _betas(beta, beta_rect)
+    if br != 0.0:
+        check(_l.lib().lqcd_gauge_force_improved(G._h, U._h, C.c_double(bp), C.c_double(br)))
+    else:
+        check(_l.lib().lqcd_gauge_force(G._h, U._h, C.c_double(bp)))
     return G
 
 
@@ -1297,9 +1334,14 @@ def Traceless_antihermitian_add_(p, factor, G):
     return p
 
 
-def P_update_(U, p, factor, beta):
-    """P_update!(U, p, eps, md) (AbstractMD.jl:99-118) in one pass: p += factor * TA(-(beta/6) U staples)."""
-    check(_l.lib().lqcd_momentum_add_gauge_force(p._h, C.c_double(factor), U._h, C.c_double(beta)))
+def P_update_(U, p, factor, beta, beta_rect=0.0):
+    """P_update!(U, p, eps, md) (AbstractMD.jl:99-118) in one pass: p += factor * TA(-(beta/6) U staples); beta may be a GaugeAction, with rectangles
+    the force of gauge_force_."""
+    bp, br = _betas(beta, beta_rect)
+    if br != 0.0:
+        check(_l.lib().lqcd_momentum_add_gauge_force_improved(p._h, C.c_double(factor), U._h, C.c_double(bp), C.c_double(br)))
+    else:
+        check(_l.lib().lqcd_momentum_add_gauge_force(p._h, C.c_double(factor), U._h, C.c_double(bp)))
     return p
 
 
