@@ -112,6 +112,10 @@ int lqcd_ctx_sync(lqcd_ctx_t ctx);
  * needs fewer or fails as on an allocation failure),
  * cg_sweep_alt (1 [default]: in a Wilson CG that runs in temporal gauge every D^+ launch walks the (pass, t) slabs of the XCD tile sweep backwards, so that each stencil launch
  * begins on the slabs the launch before it touched last; identical bits; 0: every launch forwards.  Read-only cg_sweep_alt_active: does the last CG set-up reverse its D^+),
+ * cg_store_keep_mb (256 [default]: where the CG alternates its sweep, the slabs that make up the last 256 MB of traffic of a D or D^+ launch -- the ones the next launch reads
+ * first -- store their output with plain stores and every slab before them streams it past the L2, D^+'s new residual included; 0: every store streams; -1: off, D stores by
+ * nt_store and D^+ plain; identical bits; a context that never set the key keeps -1 on launch-bound lattices (at most 1024 stencil workgroups).  Read-only
+ * cg_store_keep_active: the number of slabs that store plain in the last CG set-up, -1 if the policy is off),
  * dslash_sweep (measurement and tests; 1: every plain full-lattice application -- mul!, lqcd_bench_dslash -- that takes an eligible instance of the scalar-addressing kernel
  * walks its slabs backwards; read-only sweep_rev_active: did the last such launch),
  * dslash_xshare (1 [default]: where an x-row of a parity is 16 sites (X = 32) and x is not partitioned, the x wave of the scalar-addressing Wilson kernel -- fp64, the instances of

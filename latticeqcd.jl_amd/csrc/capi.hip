@@ -341,6 +341,8 @@ static int* param_ptr(lqcd_ctx_s* c, const char* key) {
     if (!strcmp(key, "tgauge_active")) return &c->tun.tgauge_active;
     if (!strcmp(key, "cg_sweep_alt")) return &c->tun.cg_sweep_alt;
     if (!strcmp(key, "cg_sweep_alt_active")) return &c->tun.cg_sweep_alt_active;
+    if (!strcmp(key, "cg_store_keep_mb")) return &c->tun.cg_store_keep_mb;
+    if (!strcmp(key, "cg_store_keep_active")) return &c->tun.cg_store_keep_active;
     if (!strcmp(key, "dslash_sweep")) return &c->tun.dslash_sweep;
     if (!strcmp(key, "sweep_rev_active")) return &c->tun.sweep_rev_active;
     if (!strcmp(key, "dslash_xshare")) return &c->tun.dslash_xshare;
@@ -416,6 +418,7 @@ extern "C" int lqcd_ctx_set_param(lqcd_ctx_t c, const char* key, int value) {
     if (!strcmp(key, "halo_stream_mode")) ARGCHK(value >= -1 && value <= 4, "halo_stream_mode must be -1 (timed once) or 0..4");
     if (!strcmp(key, "cg_rring")) ARGCHK(value == 0 || value == 2 || value == 4 || value == 8, "cg_rring must be 0 (off), 2, 4 or 8 (it divides the 8 iterations of a captured burst)");
     if (!strcmp(key, "cg_rring_mult")) ARGCHK((value == 1 || value == 2 || value == 4) && std::max(c->tun.cg_rring, 1) * value <= RRING_MAX, "cg_rring_mult must be 1, 2 or 4 with cg_rring x cg_rring_mult <= 32");
+    if (!strcmp(key, "cg_store_keep_mb")) ARGCHK(value >= -1, "cg_store_keep_mb: -1 (off), 0 (every store streams) or the MB of traffic at the end of a launch that store plain");
     if (!strcmp(key, "scratch_max")) ARGCHK(value >= 0, "scratch_max: 0 (no limit) or the number of work fields the scratch pool may hold");
     if (!strcmp(key, "bicg_fused")) ARGCHK(value != 3, "bicg_fused must be 0, 1, 2 or 4 (3, the grid-barrier form, was measured slower and removed)");
     if (!strcmp(key, "halo_inject_us")) ARGCHK(value >= 0 && value <= 100000, "halo_inject_us: 0..100000");
@@ -425,6 +428,7 @@ extern "C" int lqcd_ctx_set_param(lqcd_ctx_t c, const char* key, int value) {
     if (*p != value) LQCHK(links_flush_of(c));
     *p = value;
     if (!strcmp(key, "cg_rring_mult")) c->tun.cg_rring_mult_set = 1;
+    if (!strcmp(key, "cg_store_keep_mb")) c->tun.cg_store_keep_mb_set = 1;
     return LQCD_OK;
 }
 extern "C" int lqcd_ctx_get_param(lqcd_ctx_t c, const char* key, int* value) {

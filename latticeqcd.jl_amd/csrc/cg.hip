@@ -543,6 +543,7 @@ static int cg_enqueue_rring(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
         s1.upd_rec = 1;
     }
     s1.gauge12t = gt;
+    s1.keep_slabs = w.store_keep;            // (-1 unless the sweep alternates: the slabs D^+ starts on store plain, the others stream)
     s1.norm_partial = c->d_partial;
     LQCHK(stencil_apply(c, s1));
     LQCHK(reduce_to_slot(c, nbs, 1, S_PQ, true, m == 0 ? 9 : 7));      // + alpha = rr / |s|^2 into the history (9: a batch opens)
@@ -551,6 +552,7 @@ static int cg_enqueue_rring(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
     LQCHK(make_full_call(op, rn, w.tmp, 1, s2));
     s2.gauge12t = gt;
     s2.sweep_rev = w.sweep_alt ? 1 : 0;      // D^+ backwards: it starts on the slabs the D above wrote last, the next D starts on the slabs it writes last
+    s2.keep_slabs = w.store_keep;            // ... and only those store r_{k+1} plain
     s2.norm_partial = c->d_partial;
     s2.upd_scal = c->d_scal;
     for (int q = 0; q < 2; q++) { s2.upd[q] = spinor_block(rn, q); s2.upd_src[q] = spinor_block(rk, q); }
@@ -676,6 +678,7 @@ static int cg_iter_fused(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
         StencilCall s1;
         LQCHK(make_full_call(op, w.tmp, pk, 0, s1));
         s1.gauge12t = gt;
+        s1.keep_slabs = w.store_keep;      // (see cg_enqueue_rring)
         s1.norm_partial = c->d_partial;
         s1.skip_flag = c->tun.cg_skip_done ? c->d_scal : nullptr;      // a no-op once the solve has converged inside a burst
         if (fr) s1.red_slot = S_PQ;
@@ -688,6 +691,7 @@ static int cg_iter_fused(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
     LQCHK(make_full_call(op, po, w.tmp, 1, s2));          // update mode writes r only: `out` is a placeholder (the buffer that is dead until the p update)
     s2.gauge12t = gt;
     s2.sweep_rev = w.sweep_alt ? 1 : 0;      // (see cg_enqueue_rring)
+    s2.keep_slabs = w.store_keep;
     s2.norm_partial = c->d_partial;
     if (fold) s2.scal_w = c->d_scal;
     s2.upd_scal = c->d_scal;
@@ -779,6 +783,8 @@ static CgForm cg_choose_form(lqcd_op_s* op, CgWork& w) {
     return fused >= 2 ? CgForm::Fused : fused ? CgForm::NormFused : CgForm::Reference;
 }
 
+// bytes per site a stencil launch of the iteration moves in update or recurrence mode in temporal gauge: 288 of links (three directions of 12 reals), 192 each of neighbours, update source and store
+constexpr int CG_STENCIL_BYTES = 864;
 int cg_setup(lqcd_op_s* op, lqcd_spinor_s* x, lqcd_spinor_s* b, CgWork& w, double eps, double* rr0) {
     lqcd_ctx_s* c = op->ctx;
     const size_t n = x->elems;
@@ -811,6 +817,18 @@ int cg_setup(lqcd_op_s* op, lqcd_spinor_s* x, lqcd_spinor_s* b, CgWork& w, doubl
     // first use of one when t runs backwards).  Fixed here like the form: no iteration reads the tunable.
     w.sweep_alt = c->tun.cg_sweep_alt != 0 && w.tgauge && (w.form == CgForm::RRing || w.form == CgForm::Fused || w.form == CgForm::DeferX);
     c->tun.cg_sweep_alt_active = w.sweep_alt ? 1 : 0;
+    // the store policy by slab rides on it: cg_store_keep_mb of launch traffic in slabs -- a slab is 1 / nslab of the lattice, and a stencil launch of the iteration moves
+    // CG_STENCIL_BYTES per site (the 14 MB per slab of DESIGN section 4 at 32^3 x 64) -- clamped to [0, nslab].  Fixed here: a captured burst replays it unchanged
+    w.store_keep = -1;
+    if (w.sweep_alt && c->tun.cg_store_keep_mb >= 0 &&
+        (c->tun.cg_store_keep_mb_set || stencil_num_partials(c, op->kind, op->r, 2, 0, op_fused_clover(op)) > 1024)) {
+        const int nslab = stencil_sweep_slabs(c);
+        if (nslab > 0) {
+            const size_t slab_bytes = (size_t)CG_STENCIL_BYTES * (2 * (size_t)c->geom.Vh / nslab);
+            w.store_keep = (int)std::min<size_t>(((size_t)c->tun.cg_store_keep_mb << 20) / slab_bytes, (size_t)nslab);
+        }
+    }
+    c->tun.cg_store_keep_active = w.store_keep;
     w.ring = 2;
     if (w.form == CgForm::DeferX) {      // the ring of search-direction buffers (cg_defer_x = K): K - 2 more vectors, or the two-buffer form if the pool cannot grow
         int want = cg_ring_wanted(op);

@@ -553,6 +553,12 @@ struct Tunables {
                               // neighbour, link and centre streams of the first slabs of a launch are then what the launch before touched last.  Same sites, same
                               // operations per workgroup: identical bits.  0: every launch forwards
     int cg_sweep_alt_active = 0;   // read-only: 1 if the last CG set up through cg_setup reverses its D^+ launches
+    int cg_store_keep_mb = 256;    // where the CG alternates its sweep: MB of launch traffic, counted back from the end of a stencil launch, whose slabs store plain -- D's s and
+                              // D^+'s r_{k+1} alike, what the next launch reads first -- while every slab before them streams its store (StencilCall::keep_slabs; converted to
+                              // slabs and fixed in cg_setup).  0: everything streams; -1: off -- D by nt_store, D^+ plain.  Identical bits; CG at 32^3x64 +2.2 %
+                              // (profiles/r19_store_keep_ab.log).  A context that never set the key keeps -1 on launch-bound lattices (<= 1024 stencil workgroups)
+    int cg_store_keep_mb_set = 0;  // the key was set through lqcd_ctx_set_param
+    int cg_store_keep_active = -1; // read-only: the slabs that store plain in the last CG set up through cg_setup, -1 if the policy is off
     int dslash_sweep = 0;     // measurement and tests: 1 reverses the sweep of every plain full-lattice application (op_apply_async: mul!, lqcd_bench_dslash) that takes
                               // an eligible instance of the scalar-addressing kernel
     int sweep_rev_active = 0; // read-only: 1 if the last launch of the scalar-addressing kernel walked its slabs backwards
@@ -1054,6 +1060,8 @@ struct StencilCall {
     int upd_rec = 0;
     int sweep_rev = 0;            // 1: the launch walks the (pass, t) slabs of the XCD tile sweep backwards, order inside a slab kept (stencil.hip dirsplit_s_block).  Honoured by the
                                   // plain, update-mode and temporal-gauge instances of the scalar-addressing kernel with one workgroup per chunk; every other launch ignores it
+    int keep_slabs = -1;          // the same launches: >= 0, the workgroups of the last keep_slabs slabs in dispatch order store plain (the next launch of an alternating sweep starts
+                                  // on them) and every other one streams its store, update mode included; -1: the launch's own policy (nt_store; update mode: plain).  Same values
     const double* skip_flag = nullptr;  // device scalar block: the interior launch is a no-op once skip_flag[S_DONE] is set (iterations
                                         // enqueued behind the converging one in a burst)
     // small lattices (cg_small): no separate reduction launches.  The update-mode kernel sums the <= 1024 block partials of the previous
@@ -1185,6 +1193,7 @@ int gauge_ensure_recon12d(lqcd_gauge_s* g);  // (re)builds the "12 + delta" copy
 int gauge_ensure_tgauge(lqcd_gauge_s* g);    // (re)builds G and the temporal-gauge copy of the 12-real links if the field changed; sets g->tgauge_ok
 int spinor_gauge_rotate(lqcd_ctx_s* c, const double2* gfix, double2* dst, const double2* src, int adjoint);   // cg.hip: dst = G src / G^+ src on a full Wilson field (dst may be src)
 bool stencil_sdir_applies(lqcd_ctx_s* c, int kind, double r, bool clover);     // stencil.hip: a full-lattice fp64 application takes the scalar-addressing Wilson kernel (upd_src / upd_rec exist there)
+int stencil_sweep_slabs(lqcd_ctx_s* c);      // stencil.hip: slabs (pass, t) of a full-lattice launch of the scalar-addressing kernel, 0 if the map does not give any
 bool stencil_tgauge_applies(lqcd_ctx_s* c, int kind, double r, bool clover);   // stencil.hip: a full-lattice fp64 application with 12-real links would take the TG instances
 int plaquette_local_sum(lqcd_gauge_s* g, const double2* const ghost[4], double* sum);
 int gauge_pack_face(lqcd_gauge_s* g, int mu, double2* dst);

@@ -46,6 +46,8 @@ struct CgWork {
     uint64_t gauge_version = 0;
     // alternating sweep (decided once in cg_setup from the tunable cg_sweep_alt, temporal gauge only): every D^+ launch of an iteration sets StencilCall::sweep_rev
     bool sweep_alt = false;
+    // store policy by slab (tunable cg_store_keep_mb, fixed in cg_setup; only with sweep_alt): StencilCall::keep_slabs of the D and D^+ launches of an iteration, -1: off
+    int store_keep = -1;
 };
 int cg_work_get(lqcd_ctx_s* c, int kind, CgWork& w);      // the four work vectors of a solve from the context's scratch pool (the ring's extra buffers follow in cg_setup)
 void cg_work_put(CgWork& w);

@@ -384,6 +384,9 @@ struct PipeArgs {
     // eight XCDs work on at the same time -- numbered pass * LT + t in dispatch order.  sweep_rev: workgroup b runs the virtual block of slab nslab - 1 - q with its XCD, parity
     // and place inside the slab kept (StencilCall::sweep_rev)
     int sweep_rev, nslab;
+    // the same instances: the store policy by slab (StencilCall::keep_slabs).  keep_from >= 0: the workgroups of the slabs q >= keep_from in dispatch order -- the ones the next
+    // launch of an alternating sweep reads first -- store plain, every other one streams its store; -1: the launch's own policy (nt_store; update mode: plain)
+    int keep_from;
     int nvirt, both, pmode;
     int XH, L1, L2, LT, nch;
     FastDiv dXH;
@@ -794,11 +797,16 @@ __host__ __device__ constexpr bool sdir_xshare_instance(bool r12, bool delta) {
 // SIMD without scratch.  The 18-real instance (166 with the x-share alone) spills 4 VGPRs with it and keeps today's code
 __host__ __device__ constexpr bool sdir_yshare_instance(bool r12, bool delta) { return r12 && sdir_xshare_instance(r12, delta); }
 
+// the link formats whose RING instances take the store policy by slab (PipeArgs::keep_from): the 12-real ones, plain and temporal gauge -- what a CG that alternates its sweep
+// launches.  168 VGPRs, no scratch, three waves per SIMD, as without it.  The 18-real instances (166 VGPRs with it too, no spill) lost 1.2 % in the 18-real CG of bench.py
+// --full with the three results held back for one store branch, and no caller sets the policy for them: they keep their code, like 12 + delta (no reversed sweep either)
+__host__ __device__ constexpr bool sdir_keep_instance(bool r12, bool delta) { return r12 && !delta; }
+
 // TG (plain fp64 12-real instances only): the links are the temporal-gauge copy (lqcd_gauge_s::data12t) -- a time-like link is the unit matrix unless its hop crosses
 // the seam t = T - 1 -> 0, which is what s.wf / s.wb say for MU = 3 (wave-uniform): the t wave loads no link and skips the two SU(3) products and the row-2
 // rebuild everywhere else.  The boundary sign stays with pipe_sign.
 template <int MU, bool DAG, bool R12, bool NTB, bool DOT = false, bool DELTA = false, bool DW5 = false, bool FOLD = false, bool CINV = false, bool TG = false>
-__device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int lane, real al_upd, real& nrm, real& dre, real& dim, int vb, real& dre2, real& dim2) {
+__device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int lane, real al_upd, real& nrm, real& dre, real& dim, int vb, real& dre2, real& dim2, int keep = -1) {
     // DW5: this workgroup's slice s5 of the five-dimensional fields; block ids keep their XCD (b & 7) and the L5 slices of a chunk follow each other on it, so the
     // links of the chunk are fetched from the fabric once and hit the XCD's L2 for the other slices
     int vblock = vb, s5 = 0;      // (vb: blockIdx.x, or the entry of the bulk / boundary list of a folded launch)
@@ -843,6 +851,10 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
     const bool ysh = YSI && a_.xshare != 0 && a_.yshare != 0;      // (wave-uniform, and the same value in the four waves)
     constexpr bool YS = MU == 1 && YSI;
     const bool ys = YS && ysh;
+    // store policy by slab (PipeArgs::keep_from): keep = 1, this workgroup's slab is one the next launch starts on: plain stores; 0: streamed stores, update mode included;
+    // -1: the launch's own policy (nt_store; update mode: plain).  The instances that take it (KEEP: those of the reversed sweep with 12-real links) decide ONCE per wave, on
+    // the scalar unit, and hold the three results back for one branch around three stores; every other instance keeps its store per component
+    constexpr bool KEEP = RING && sdir_keep_instance(R12, DELTA);
     const size_t gpar = (size_t)a.nch * 4 * NL * 64;
     const PipeSite s = pipe_site<MU, NL>(a, vblock, lane);
     cd xv[3] = {mk(0, 0), mk(0, 0), mk(0, 0)}, rv[3] = {mk(0, 0), mk(0, 0), mk(0, 0)};
@@ -1188,6 +1200,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
             __builtin_amdgcn_sched_barrier(0);
         }
     }
+    cd ov[KEEP ? 3 : 1];
 #pragma unroll
     for (int cc = 0; cc < 3; cc++) {
         const int j = 3 * MU + cc;
@@ -1212,15 +1225,31 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
             if (RING && a.rec) {      // recurrence mode: s = v + beta s_old over s_old (al_upd = beta), |s|^2, the plain launch's store policy
                 r.re = fma(al_upd, r.re, v.re); r.im = fma(al_upd, r.im, v.im);
                 nrm = fma(r.re, r.re, nrm); nrm = fma(r.im, r.im, nrm);
-                if (a.nt_store) st_nt(dstp + co12(j), r); else st(dstp + co12(j), r);
+                if constexpr (KEEP) ov[cc] = r;
+                else { if (a.nt_store) st_nt(dstp + co12(j), r); else st(dstp + co12(j), r); }
             } else {
                 r.re = fma(-al_upd, v.re, r.re); r.im = fma(-al_upd, v.im, r.im);
                 nrm = fma(r.re, r.re, nrm); nrm = fma(r.im, r.im, nrm);
-                st(dstp + co12(j), r);
+                if constexpr (KEEP) ov[cc] = r;
+                else st(dstp + co12(j), r);
             }
         } else {
             nrm = fma(v.re, v.re, nrm); nrm = fma(v.im, v.im, nrm);
-            if (a.nt_store) st_nt(dstp + co12(j), v); else st(dstp + co12(j), v);
+            if constexpr (KEEP) ov[cc] = v;
+            else { if (a.nt_store) st_nt(dstp + co12(j), v); else st(dstp + co12(j), v); }
+        }
+    }
+    if constexpr (KEEP) {
+        // update mode stores plain (the next D reads r as its hop operand), recurrence mode and the plain launch by nt_store; under the slab policy keep = 1 stores plain
+        // and keep = 0 streams -- update mode always, the other two where nt_store allows it (small volumes keep their plain stores)
+        const bool updm = a.upd_scal != nullptr && !a.rec;
+        const bool nt_out = keep < 0 ? (a.nt_store && !updm) : (keep == 0 && (a.nt_store || updm));
+        if (nt_out) {
+#pragma unroll
+            for (int cc = 0; cc < 3; cc++) st_nt(dstp + co12(3 * MU + cc), ov[cc]);
+        } else {
+#pragma unroll
+            for (int cc = 0; cc < 3; cc++) st(dstp + co12(3 * MU + cc), ov[cc]);
         }
     }
 }
@@ -1258,24 +1287,31 @@ __device__ __forceinline__ void dirsplit_s_block(const PipeArgs& a, real2 (*part
     // Reversed sweep (PipeArgs::sweep_rev), on the scalar unit: only pass and t are mirrored.  The order inside a slab stays -- the streaming
     // hint on the backward use of a link (NTB) assumes that use is the later one, and mirroring z or y would put it on the first (LABNOTES: 0.60 against 0.41 ms).  Everything
     // downstream -- pipe_site, the partial index -- runs on the virtual block; the done-flag tests above stay keyed on blockIdx.x.
+    // Store policy by slab (PipeArgs::keep_from), the same instances: the slab in DISPATCH order decides, forwards and backwards -- the last slabs a launch runs are the first
+    // ones the next launch of the alternating sweep reads.
+    int keep = -1;
     if constexpr (!DOT && !DELTA && !DW5 && !FOLD && !CINV) {
-        if (a.sweep_rev) {
+        constexpr bool KI = sdir_keep_instance(R12, DELTA);
+        if (a.sweep_rev || (KI && a.keep_from >= 0)) {
             int j = vb >> 3;
             const int pb = a.both ? (j & 1) : 0;
             j = a.both ? (j >> 1) : j;
             const int q = fdiv_nb(j, a.d_cpr);       // this workgroup's slab in dispatch order
-            j += (a.nslab - 1 - 2 * q) * a.cpr;      // slab nslab - 1 - q, same place inside it
-            vb = ((a.both ? 2 * j + pb : j) << 3) | (vb & 7);
+            if (KI && a.keep_from >= 0) keep = q >= a.keep_from ? 1 : 0;
+            if (a.sweep_rev) {
+                j += (a.nslab - 1 - 2 * q) * a.cpr;      // slab nslab - 1 - q, same place inside it
+                vb = ((a.both ? 2 * j + pb : j) << 3) | (vb & 7);
+            }
         }
     }
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     real nrm = 0.0, dre = 0.0, dim = 0.0, dre2 = 0.0, dim2 = 0.0;
     switch (w) {
-    case 0: sdir_wave<0, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2); break;
-    case 1: sdir_wave<1, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2); break;
-    case 2: sdir_wave<2, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2); break;
-    default: sdir_wave<3, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2); break;
+    case 0: sdir_wave<0, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2, keep); break;
+    case 1: sdir_wave<1, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2, keep); break;
+    case 2: sdir_wave<2, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2, keep); break;
+    default: sdir_wave<3, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2, keep); break;
     }
     if constexpr (DOT) {                // three sums per workgroup, the order of wilson_dirsplit's dot epilogue; five with a second inner product (dot_z2)
         const bool five = a.dotz2[0] != nullptr || a.dotz2[1] != nullptr;
@@ -1955,7 +1991,7 @@ static PipeArgs make_pipe_args(lqcd_ctx_s* c, const KArgs& k, const StencilCall&
     a.nt_store = (k.nt & 4) != 0;
     a.nt_centre = c->tun.nt_centre != 0;
     a.xshare = 0; a.yshare = 0;        // (set by pipe_xshare_args for the launches of the RING instances)
-    a.sweep_rev = 0; a.nslab = 0;      // (set by the one launch site that honours StencilCall::sweep_rev)
+    a.sweep_rev = 0; a.nslab = 0; a.keep_from = -1;      // (set by the one launch site that honours StencilCall::sweep_rev and keep_slabs)
     a.nvirt = k.nblocks; a.both = s.parity_mode == 2; a.pmode = s.parity_mode == 2 ? 0 : s.parity_mode;
     a.XH = k.g.XH; a.L1 = k.g.L[1]; a.L2 = k.g.L[2]; a.LT = k.g.L[3]; a.nch = k.g.nch; a.dXH = k.g.dXH;
     for (int mu = 0; mu < 4; mu++) {
@@ -1981,17 +2017,22 @@ static PipeArgs make_pipe_args(lqcd_ctx_s* c, const KArgs& k, const StencilCall&
     return a;
 }
 
+static int pipe_nslab(const KArgs& k, int par) {      // slabs (pass, t) of a launch of k.nblocks workgroups; 0: its blocks are not whole slabs of the map
+    const bool map_ok = k.cps > 0 && k.cpr > 0 && k.nblocks % (8 * par * k.cpr) == 0 && k.nblocks / (8 * par * k.cpr) == (k.nsub / 8) * k.g.L[3];
+    return map_ok ? k.nblocks / (8 * par * k.cpr) : 0;
+}
 // The reversed sweep (StencilCall::sweep_rev) of the scalar-addressing kernel with one workgroup per chunk: the slabs of the launch.  Honoured by the plain, update-mode
-// and temporal-gauge instances only (dslash_pipe = 2; not the five-dimensional, folded and 12 + delta launches).
+// and temporal-gauge instances only (dslash_pipe = 2; not the five-dimensional, folded and 12 + delta launches).  The store policy by slab (StencilCall::keep_slabs) goes
+// with it: the same launches with 12-real links (sdir_keep_instance), the last keep_slabs slabs in dispatch order.
 static void pipe_sweep_args(lqcd_ctx_s* c, const KArgs& k, const StencilCall& s, bool delta, PipeArgs& a) {
     const int par = s.parity_mode == 2 ? 2 : 1;
     const bool plain = c->tun.dslash_pipe == 2 && s.dw_ls <= 1 && !s.fold && !delta;
-    const bool map_ok = k.cps > 0 && k.cpr > 0 && k.nblocks % (8 * par * k.cpr) == 0 && k.nblocks / (8 * par * k.cpr) == (k.nsub / 8) * k.g.L[3];
-    a.nslab = map_ok ? k.nblocks / (8 * par * k.cpr) : 0;
-    a.sweep_rev = 0;
-    if (!plain || !map_ok) return;
+    a.nslab = pipe_nslab(k, par);
+    a.sweep_rev = 0; a.keep_from = -1;
+    if (!plain || a.nslab == 0) return;
     a.sweep_rev = s.sweep_rev ? 1 : 0;
     c->tun.sweep_rev_active = a.sweep_rev;
+    if (s.keep_slabs >= 0 && sdir_keep_instance(k.gauge12 != nullptr, delta)) a.keep_from = a.nslab - std::min(s.keep_slabs, a.nslab);
 }
 
 // The x-share of the scalar-addressing kernel's x wave (sdir_wave, PipeArgs::xshare): offered by the RING instances of the fp64 build, one workgroup per chunk, where an
@@ -2419,6 +2460,13 @@ bool wilson_pipe_applies(lqcd_ctx_s* c, int kind, double r, int parity_mode, boo
 bool stencil_sdir_applies(lqcd_ctx_s* c, int kind, double r, bool clover) {
     if (any_partitioned(c) || c->has_comm || c->tun.dslash_pipe != 2 || !(c->tun.gauge_recon == 12 || c->tun.dslash_s18)) return false;
     return wilson_pipe_applies(c, kind, r, 2, clover);
+}
+// slabs (pass, t) of a full-lattice launch of the scalar-addressing kernel with one workgroup per chunk (PipeArgs::nslab); 0: the map does not split the launch into slabs
+int stencil_sweep_slabs(lqcd_ctx_s* c) {
+    if (c->tun.dslash_pipe != 2) return 0;
+    StencilCall s = StencilCall();
+    s.parity_mode = 2;
+    return pipe_nslab(make_kargs(c, s, 64), 2);
 }
 bool stencil_tgauge_applies(lqcd_ctx_s* c, int kind, double r, bool clover) {
     if (any_partitioned(c) || c->tun.dslash_pipe != 2 || c->tun.gauge_recon != 12 || c->geom.L[3] < 2) return false;
