@@ -135,7 +135,11 @@ int lqcd_ctx_sync(lqcd_ctx_t ctx);
  * unpartitioned lattice of more than 1024 stencil workgroups, 12-real links active, scalar-addressing kernel -- iterates in temporal gauge: x0 and b are colour-rotated by G(x, t) = U_t(x, 0) ... U_t(x, t - 1),
  * the stencils read a rotated 12-real copy of the links, cached per version of the field, and skip the time-like links below the last time slice (they are unit matrices), and x is rotated back on exit; the
  * iterates equal the unrotated ones to rounding, b is not written; the copy must pass the 1e-14 gates of the 12-real links, else the solve runs unrotated; 0: off; 2: on small lattices too [tests];
- * read-only tgauge_active: the last CG ran rotated.  An open CG session fails at its next lqcd_cg_session_iterate if the gauge field was changed under it), clover_fused (1 [default]: A x in the epilogue of the split kernel), clover_transport (1: partitioned-lattice
+ * read-only tgauge_active: the last CG ran rotated.  cg_tgauge_recon (8 [default] | 12): reals per link that solve reads -- 8: a second copy of the rotated links, 64 B per link instead of 96, row 0 as the
+ * stereographic image of a point of S^5, row 1 as a point of S^3 in the frame of row 0's Householder reflector, row 2 rebuilt as for 12; used by the residual-ring and cg_fused = 2 forms for EVERY stencil
+ * launch of a solve or for none (read-only tgauge_recon_active: 8, 12, or 0 without temporal gauge), only while the copy rebuilds every entry of every link to 10^-tgauge8_gate_e (14 [default]; larger values force
+ * 12 reals: tests; the measured maximum: lqcd_gauge_tgauge8_deviation), and, unless the key was set, only beyond 1024 stencil workgroups; the iterates agree with the 12-real solve to rounding, not bit for bit.
+ * An open CG session fails at its next lqcd_cg_session_iterate if the gauge field was changed under it), clover_fused (1 [default]: A x in the epilogue of the split kernel), clover_transport (1: partitioned-lattice
  * construction of the clover term / force also on one rank);
  * partitioned lattices: halo_merge (1 [default]: one message per peer when both faces go to the same rank), halo_stream_mode
  * (-1 [default]: time the four schedules of the halo exchange once -- collectively: every rank adopts the schedule with the smallest time summed over
@@ -200,6 +204,10 @@ int lqcd_gauge_plaquette(lqcd_gauge_t g, double* plaq);                   /* cal
 /* diagnostic, no reference counterpart: max over all links and elements of |row2 - conj(row0 x row1)| -- the quantity the 12-real link
  * path (tunable gauge_recon) is gated on (<= 1e-14 on every link); this rank's sub-lattice only */
 int lqcd_gauge_unitarity_deviation(lqcd_gauge_t g, double* maxdev);
+/* diagnostic: builds (once per version of the field) the temporal-gauge copy of the links and its 8-real form, and returns the gate of the latter: max over all
+ * links and all nine entries of |decode(encode(U')) - U'| -- the 8-real temporal-gauge CG (tunable cg_tgauge_recon) runs while it is <= 10^-tgauge8_gate_e.
+ * 1e300: a link on a pole of the chart, no 12-real temporal-gauge copy (its own gate failed, partitioned lattice), or no memory for the 8-real one */
+int lqcd_gauge_tgauge8_deviation(lqcd_gauge_t g, double* maxdev);
 
 /* ---------------------------------------------------------------- fermion fields (Initialize_pseudofermion_fields, universe.jl:107,112) */
 int lqcd_spinor_create(lqcd_ctx_t ctx, lqcd_spinor_t* s, int kind, int subset);

@@ -419,11 +419,12 @@ int check_full(lqcd_op_s* op, lqcd_spinor_s* a, lqcd_spinor_s* b, const char* wh
     return links_flush_of(op);      // the operator reads its links: recorded single-direction link operations run first (links.hip)
 }
 
-int op_apply_async(lqcd_op_s* op, lqcd_spinor_s* out, lqcd_spinor_s* in, int dagger, double* norm_partial, const double* skip_flag, const double2* gauge12t) {
+int op_apply_async(lqcd_op_s* op, lqcd_spinor_s* out, lqcd_spinor_s* in, int dagger, double* norm_partial, const double* skip_flag, const double2* gauge12t, const double2* gauge8t) {
     apply_bc(op->ctx, op->bc);
     StencilCall s;
     LQCHK(make_full_call(op, out, in, dagger, s));
     s.gauge12t = gauge12t;      // the CG in temporal gauge: `in` and `out` are rotated vectors
+    s.gauge8t = gauge8t;        // ... and its 8-real solve
     s.norm_partial = norm_partial;
     s.skip_flag = skip_flag;
     s.sweep_rev = op->ctx->tun.dslash_sweep != 0;      // (measurement and tests: off by default)

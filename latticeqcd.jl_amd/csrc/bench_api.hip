@@ -173,7 +173,7 @@ extern "C" int lqcd_bench_cg(lqcd_op_t op, lqcd_spinor_t x, lqcd_spinor_t b, int
 }
 
 // one launch of a full-lattice stencil with the epilogues the fused CG uses, on caller-owned fields (tests): mode 0 plain, dst = D in; 1 update mode, dst = src - coef D in
-// (src may be dst: the in-place launch); 2 recurrence mode, dst = D in + coef dst.  D^+ with dagger, the temporal-gauge copy of the links with tgauge, `done` is written to
+// (src may be dst: the in-place launch); 2 recurrence mode, dst = D in + coef dst.  D^+ with dagger, the temporal-gauge copy of the links with tgauge (8: its 8-real form), `done` is written to
 // the done flag first (modes 1 and 2 are then no-ops) and cleared afterwards.  norm2: the sum of the launch's |.|^2 partials.
 extern "C" int lqcd_bench_stencil_epilogue(lqcd_op_t op, lqcd_spinor_t dst, lqcd_spinor_t src, lqcd_spinor_t in, int dagger, int mode, int tgauge, double coef, int done, double* norm2) {
     LQCHK(check_full(op, dst, in, "lqcd_bench_stencil_epilogue"));
@@ -182,10 +182,14 @@ extern "C" int lqcd_bench_stencil_epilogue(lqcd_op_t op, lqcd_spinor_t dst, lqcd
     ARGCHK(in != dst && in != src, "lqcd_bench_stencil_epilogue: the hop operand must not be written");
     lqcd_ctx_s* c = op->ctx;
     HIPCHK(hipSetDevice(c->device));
-    const double2* gt = nullptr;
+    const double2 *gt = nullptr, *gt8 = nullptr;
     if (tgauge) {
         ARGCHK(gauge_ensure_tgauge(op->gauge) == LQCD_OK && op->gauge->tgauge_ok, "lqcd_bench_stencil_epilogue: no temporal-gauge copy of these links");
         gt = op->gauge->data12t;
+        if (tgauge == 8) {      // ... in its 8-real form
+            ARGCHK(gauge_ensure_tgauge(op->gauge, true) == LQCD_OK && op->gauge->data8t && op->gauge->tgauge8_dev <= 1e-14, "lqcd_bench_stencil_epilogue: no 8-real temporal-gauge copy of these links");
+            gt8 = op->gauge->data8t;
+        }
     }
     double sc[3] = {coef, coef, done ? 1.0 : 0.0};      // S_ALPHA, S_BETA, S_DONE
     static_assert(S_BETA == S_ALPHA + 1 && S_DONE == S_ALPHA + 2, "lqcd_bench_stencil_epilogue: scalar slots");
@@ -194,6 +198,7 @@ extern "C" int lqcd_bench_stencil_epilogue(lqcd_op_t op, lqcd_spinor_t dst, lqcd
     StencilCall s;
     LQCHK(make_full_call(op, dst, in, dagger, s));
     s.gauge12t = gt;
+    s.gauge8t = gt8;
     s.norm_partial = c->d_partial;
     if (mode) {
         s.upd_scal = c->d_scal;

@@ -281,7 +281,7 @@ extern "C" int lqcd_ctx_destroy(lqcd_ctx_t c) {
     }
     for (void* b : c->mix_buf) (void)hipFree(b);
     (void)hipFree(c->clover_q[0]); (void)hipFree(c->clover_q[1]);
-    for (lqcd_gauge_s*& t : c->stout_tmp) if (t) { (void)hipFree(t->data); (void)hipFree(t->data12); (void)hipFree(t->data12d); (void)hipFree(t->data12t); (void)hipFree(t->gfix); delete t; t = nullptr; }
+    for (lqcd_gauge_s*& t : c->stout_tmp) if (t) { (void)hipFree(t->data); (void)hipFree(t->data12); (void)hipFree(t->data12d); (void)hipFree(t->data12t); (void)hipFree(t->data8t); (void)hipFree(t->gfix); delete t; t = nullptr; }
     (void)hipFree(c->gauge_spare);
     (void)hipFree(c->flow_x); (void)hipFree(c->flow_partial); (void)hipFree(c->flow_tab);
     (void)hipFree(c->hb_tab);
@@ -339,6 +339,9 @@ static int* param_ptr(lqcd_ctx_s* c, const char* key) {
     if (!strcmp(key, "cg_small")) return &c->tun.cg_small;
     if (!strcmp(key, "cg_tgauge")) return &c->tun.cg_tgauge;
     if (!strcmp(key, "tgauge_active")) return &c->tun.tgauge_active;
+    if (!strcmp(key, "cg_tgauge_recon")) return &c->tun.cg_tgauge_recon;
+    if (!strcmp(key, "tgauge_recon_active")) return &c->tun.tgauge_recon_active;
+    if (!strcmp(key, "tgauge8_gate_e")) return &c->tun.tgauge8_gate_e;
     if (!strcmp(key, "cg_sweep_alt")) return &c->tun.cg_sweep_alt;
     if (!strcmp(key, "cg_sweep_alt_active")) return &c->tun.cg_sweep_alt_active;
     if (!strcmp(key, "cg_store_keep_mb")) return &c->tun.cg_store_keep_mb;
@@ -419,6 +422,8 @@ extern "C" int lqcd_ctx_set_param(lqcd_ctx_t c, const char* key, int value) {
     if (!strcmp(key, "cg_rring")) ARGCHK(value == 0 || value == 2 || value == 4 || value == 8, "cg_rring must be 0 (off), 2, 4 or 8 (it divides the 8 iterations of a captured burst)");
     if (!strcmp(key, "cg_rring_mult")) ARGCHK((value == 1 || value == 2 || value == 4) && std::max(c->tun.cg_rring, 1) * value <= RRING_MAX, "cg_rring_mult must be 1, 2 or 4 with cg_rring x cg_rring_mult <= 32");
     if (!strcmp(key, "cg_store_keep_mb")) ARGCHK(value >= -1, "cg_store_keep_mb: -1 (off), 0 (every store streams) or the MB of traffic at the end of a launch that store plain");
+    if (!strcmp(key, "cg_tgauge_recon")) ARGCHK(value == 12 || value == 8, "cg_tgauge_recon must be 12 or 8 (reals per link the temporal-gauge CG reads)");
+    if (!strcmp(key, "tgauge8_gate_e")) ARGCHK(value >= 1 && value <= 300, "tgauge8_gate_e: the 8-real copy is used when its deviation is <= 10^-e, e in 1..300");
     if (!strcmp(key, "scratch_max")) ARGCHK(value >= 0, "scratch_max: 0 (no limit) or the number of work fields the scratch pool may hold");
     if (!strcmp(key, "bicg_fused")) ARGCHK(value != 3, "bicg_fused must be 0, 1, 2 or 4 (3, the grid-barrier form, was measured slower and removed)");
     if (!strcmp(key, "halo_inject_us")) ARGCHK(value >= 0 && value <= 100000, "halo_inject_us: 0..100000");
@@ -429,6 +434,7 @@ extern "C" int lqcd_ctx_set_param(lqcd_ctx_t c, const char* key, int value) {
     *p = value;
     if (!strcmp(key, "cg_rring_mult")) c->tun.cg_rring_mult_set = 1;
     if (!strcmp(key, "cg_store_keep_mb")) c->tun.cg_store_keep_mb_set = 1;
+    if (!strcmp(key, "cg_tgauge_recon")) c->tun.cg_tgauge_recon_set = 1;
     return LQCD_OK;
 }
 extern "C" int lqcd_ctx_get_param(lqcd_ctx_t c, const char* key, int* value) {

@@ -506,7 +506,9 @@ int cg_finish(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w, bool flush) {
     }
     return st;
 }
-bool cg_gauge_moved(lqcd_op_s* op, const CgWork& w) { return w.tgauge && (op->gauge->version != w.gauge_version || op->gauge->data12t != w.links_t); }
+bool cg_gauge_moved(lqcd_op_s* op, const CgWork& w) {
+    return w.tgauge && (op->gauge->version != w.gauge_version || op->gauge->data12t != w.links_t || (w.links_t8 && op->gauge->data8t != w.links_t8));
+}
 
 // The solve runs in temporal gauge when: Wilson, r = 1, no clover term, unpartitioned lattice, the stencil launches of the iteration take the TG instances
 // (asked before anything is rotated), the rotated copy of this version of the links passed its gate, and the tunable cg_tgauge allows it -- 1: beyond the
@@ -543,6 +545,7 @@ static int cg_enqueue_rring(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
         s1.upd_rec = 1;
     }
     s1.gauge12t = gt;
+    s1.gauge8t = w.links_t8;
     s1.keep_slabs = w.store_keep;            // (-1 unless the sweep alternates: the slabs D^+ starts on store plain, the others stream)
     s1.norm_partial = c->d_partial;
     LQCHK(stencil_apply(c, s1));
@@ -551,6 +554,7 @@ static int cg_enqueue_rring(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
     StencilCall s2;
     LQCHK(make_full_call(op, rn, w.tmp, 1, s2));
     s2.gauge12t = gt;
+    s2.gauge8t = w.links_t8;
     s2.sweep_rev = w.sweep_alt ? 1 : 0;      // D^+ backwards: it starts on the slabs the D above wrote last, the next D starts on the slabs it writes last
     s2.keep_slabs = w.store_keep;            // ... and only those store r_{k+1} plain
     s2.norm_partial = c->d_partial;
@@ -678,6 +682,7 @@ static int cg_iter_fused(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
         StencilCall s1;
         LQCHK(make_full_call(op, w.tmp, pk, 0, s1));
         s1.gauge12t = gt;
+        s1.gauge8t = w.links_t8;
         s1.keep_slabs = w.store_keep;      // (see cg_enqueue_rring)
         s1.norm_partial = c->d_partial;
         s1.skip_flag = c->tun.cg_skip_done ? c->d_scal : nullptr;      // a no-op once the solve has converged inside a burst
@@ -690,6 +695,7 @@ static int cg_iter_fused(lqcd_op_s* op, lqcd_spinor_s* x, CgWork& w) {
     StencilCall s2;
     LQCHK(make_full_call(op, po, w.tmp, 1, s2));          // update mode writes r only: `out` is a placeholder (the buffer that is dead until the p update)
     s2.gauge12t = gt;
+    s2.gauge8t = w.links_t8;
     s2.sweep_rev = w.sweep_alt ? 1 : 0;      // (see cg_enqueue_rring)
     s2.keep_slabs = w.store_keep;
     s2.norm_partial = c->d_partial;
@@ -783,7 +789,22 @@ static CgForm cg_choose_form(lqcd_op_s* op, CgWork& w) {
     return fused >= 2 ? CgForm::Fused : fused ? CgForm::NormFused : CgForm::Reference;
 }
 
+// The temporal-gauge solve reads 8 reals per link (lqcd_gauge_s::data8t) when EVERY stencil launch of it takes the TG8 instance -- the set-up applications, the plain D behind
+// a batch, recurrence D and D^+: the residual-ring, Fused and DeferX forms -- the tunable cg_tgauge_recon says 8 (unset: beyond 1024 stencil workgroups only, so that small
+// lattices keep the bits of the 12-real solve), and the 8-real copy of this version of the links exists and passed its gate (tgauge8_gate_e).  Anything else -- cg_small,
+// the forms on op_apply_async, a failed gate or allocation -- reads 12 reals throughout: a solve never mixes the two operators.  Returns the copy, or nullptr.
+static const double2* cg_tgauge8_links(lqcd_op_s* op, const CgWork& w) {
+    lqcd_ctx_s* c = op->ctx;
+    if (!w.tgauge || c->tun.cg_tgauge_recon != 8) return nullptr;
+    if (!(w.form == CgForm::RRing || w.form == CgForm::Fused || w.form == CgForm::DeferX)) return nullptr;
+    if (!c->tun.cg_tgauge_recon_set && stencil_num_partials(c, op->kind, op->r, 2, 0, op_fused_clover(op)) <= 1024) return nullptr;
+    lqcd_gauge_s* g = op->gauge;
+    if (gauge_ensure_tgauge(g, true) != LQCD_OK || !g->data8t) return nullptr;
+    return g->tgauge8_dev <= std::pow(10.0, -(double)c->tun.tgauge8_gate_e) ? g->data8t : nullptr;
+}
+
 // bytes per site a stencil launch of the iteration moves in update or recurrence mode in temporal gauge: 288 of links (three directions of 12 reals), 192 each of neighbours, update source and store
+// (192 of links in the 8-real solve: the store policy keeps its slab count in MB of the 12-real launch)
 constexpr int CG_STENCIL_BYTES = 864;
 int cg_setup(lqcd_op_s* op, lqcd_spinor_s* x, lqcd_spinor_s* b, CgWork& w, double eps, double* rr0) {
     lqcd_ctx_s* c = op->ctx;
@@ -795,10 +816,15 @@ int cg_setup(lqcd_op_s* op, lqcd_spinor_s* x, lqcd_spinor_s* b, CgWork& w, doubl
     w.links_t = w.tgauge ? op->gauge->data12t : nullptr;
     w.gfix = w.tgauge ? op->gauge->gfix : nullptr;
     w.gauge_version = op->gauge->version;
+    // the iteration form, ahead of the set-up applications: the link format of the whole solve hangs on it (RRing: sets the depth w.rring = K M and w.rring_k = K)
+    w.rring = w.rring_k = 0;
+    w.form = cg_choose_form(op, w);
+    w.links_t8 = cg_tgauge8_links(op, w);
+    c->tun.tgauge_recon_active = w.tgauge ? (w.links_t8 ? 8 : 12) : 0;
     if (w.tgauge) LQCHK(spinor_gauge_rotate(c, w.gfix, x->data, x->data, 0));
     // r = b - D^+ D x ; p = r
-    LQCHK(op_apply_async(op, w.tmp, x, 0, nullptr, nullptr, w.links_t));
-    LQCHK(op_apply_async(op, w.q, w.tmp, 1, nullptr, nullptr, w.links_t));
+    LQCHK(op_apply_async(op, w.tmp, x, 0, nullptr, nullptr, w.links_t, w.links_t8));
+    LQCHK(op_apply_async(op, w.q, w.tmp, 1, nullptr, nullptr, w.links_t, w.links_t8));
     if (w.tgauge) LQCHK(spinor_gauge_rotate(c, w.gfix, w.r->data, b->data, 0));
     else HIPCHK(hipMemcpyAsync(w.r->data, b->data, n * sizeof(double2), hipMemcpyDeviceToDevice, c->stream));
     LQCHK(blas_axpy(c, -1.0, 0.0, w.q->data, w.r->data, n));
@@ -809,8 +835,6 @@ int cg_setup(lqcd_op_s* op, lqcd_spinor_s* x, lqcd_spinor_s* b, CgWork& w, doubl
     HIPCHK(hipMemcpyAsync(c->d_scal + S_RR, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     w.k = 0; w.p_packed = false; w.flushed = false;
-    w.rring = w.rring_k = 0;
-    w.form = cg_choose_form(op, w);      // (RRing: sets the depth w.rring = K M and w.rring_k = K)
     c->tun.cg_rring_active = w.rring_k;
     c->tun.cg_rring_depth_active = w.rring;
     // the alternating sweep: the forms whose D^+ is a launch of the temporal-gauge instance (away from the seam it loads no time-like link, so no streaming hint sits on the

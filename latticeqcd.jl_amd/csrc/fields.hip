@@ -280,6 +280,7 @@ int gauge_destroy_now(lqcd_gauge_s* g) {
     (void)hipFree(g->data12);
     (void)hipFree(g->data12d);
     (void)hipFree(g->data12t);
+    (void)hipFree(g->data8t);
     (void)hipFree(g->gfix);
     delete g;
     return LQCD_OK;
@@ -473,6 +474,13 @@ extern "C" int lqcd_gauge_unitarity_deviation(lqcd_gauge_t g, double* maxdev) {
     ARGCHK(g && maxdev, "lqcd_gauge_unitarity_deviation: null argument");
     LQCHK(lqcd::gauge_ensure_recon12(g));      // measured by the pass that builds the 12-real copy (once per version of the field)
     *maxdev = g->recon_dev;
+    return LQCD_OK;
+}
+extern "C" int lqcd_gauge_tgauge8_deviation(lqcd_gauge_t g, double* maxdev) {
+    LQCHK(lqcd::links_flush_of(g));
+    ARGCHK(g && maxdev, "lqcd_gauge_tgauge8_deviation: null argument");
+    LQCHK(lqcd::gauge_ensure_tgauge(g, true));      // measured by the gate behind the encode pass (once per version of the field)
+    *maxdev = g->tgauge8_dev;
     return LQCD_OK;
 }
 
@@ -716,9 +724,97 @@ __global__ __launch_bounds__(256) void tgauge_rotate_links(Geom g, const double2
     if ((threadIdx.x & 63) == 0 && dev > 0.0) atomicMax(maxdev, (unsigned long long)__double_as_longlong(dev));
 }
 
-int gauge_ensure_tgauge(lqcd_gauge_s* g) {
+// The 8-real form of the rotated links (link8_decode, lqcd_internal.h).  Encode, lane = site, blockIdx.y = (parity, mu): X from row a with 1 - Im a3 taken as
+// sum x_i^2 / (1 + Im a3) where Im a3 > 0 (relative precision near the pole); a', phi, tau from X with the decode function itself; (c1, c2) = rows 1, 2 of H b with
+// the reflector of a', normalised; Y from it the same way.  A link on a pole (a3 = i or c2 = i exactly) stores infinities, which the gate below reads as a failure.
+__device__ inline void link8_stereo(const double (&x)[5], double x6, double (&X)[5], int n) {      // the first n of x (the rest are padding zeros)
+    double ss = 0.0;
+#pragma unroll
+    for (int j = 0; j < 5; j++) if (j < n) ss = fma(x[j], x[j], ss);
+    const double om = x6 > 0.0 ? ss / (1.0 + x6) : 1.0 - x6;
+#pragma unroll
+    for (int j = 0; j < 5; j++) X[j] = j < n ? x[j] / om : 0.0;
+}
+__global__ __launch_bounds__(256) void tgauge8_encode(Geom g, const double2* __restrict__ u12t, double2* __restrict__ dst) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, p = blockIdx.y >> 2, mu = blockIdx.y & 3;
+    if (i >= g.Vh) return;
+    const double2* src = u12t + glink12_off(g, p, mu, i);
+    cd a[3], b[3];
+#pragma unroll
+    for (int e = 0; e < 3; e++) { a[e] = ld(src + (size_t)e * 64); b[e] = ld(src + (size_t)(3 + e) * 64); }
+    const double xa[5] = {a[0].re, a[1].re, a[2].re, a[0].im, a[1].im};
+    double X[5];
+    link8_stereo(xa, a[2].im, X, 5);
+    cd w[4] = {mk(X[0], X[3]), mk(X[1], X[4]), mk(X[2], 0.0), mk(0.0, 0.0)}, u[9], phi;
+    double tau, big;
+    link8_decode(w, u, phi, tau, big);      // a' = u[0..2]: the row the stencils will see
+    const cd v1 = u[0] + phi;
+    cd q = mk(0.0, 0.0);                   // v^+ b
+    cfma_conj(q, v1, b[0]); cfma_conj(q, u[1], b[1]); cfma_conj(q, u[2], b[2]);
+    const cd tq = mk(tau * q.re, tau * q.im);
+    cd c1 = b[1], c2 = b[2];
+    cfma(c1, mk(-u[1].re, -u[1].im), tq);
+    cfma(c2, mk(-u[2].re, -u[2].im), tq);
+    double nn = c1.re * c1.re; nn = fma(c1.im, c1.im, nn); nn = fma(c2.re, c2.re, nn); nn = fma(c2.im, c2.im, nn);
+    const double in = 1.0 / sqrt(nn);
+    const double xc[5] = {in * c1.re, in * c1.im, in * c2.re, 0.0, 0.0};
+    double Y[5];
+    link8_stereo(xc, in * c2.im, Y, 3);
+    w[2].im = Y[2];
+    w[3] = mk(Y[0], Y[1]);
+    double2* d = dst + ((((size_t)p * g.nch + (size_t)(i >> 6)) * 4 + mu) * 4) * 64 + (i & 63);
+#pragma unroll
+    for (int e = 0; e < 4; e++) st(d + (size_t)e * 64, w[e]);
+}
+// the gate: every link decoded from memory as the stencils decode it, row 2 rebuilt, against the 12-real copy with its row 2; *maxdev as in tgauge_rotate_links, 1e300
+// for a link that is not finite or whose |X|^2 or |Y|^2 exceeds 1e30
+__global__ __launch_bounds__(256) void tgauge8_gate(Geom g, const double2* __restrict__ u12t, const double2* __restrict__ u8t, unsigned long long* maxdev) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, p = blockIdx.y >> 2, mu = blockIdx.y & 3;
+    double dev = 0.0;
+    if (i < g.Vh) {
+        cd ref[9], u[9], w[4], phi;
+        tg_load12(ref, u12t + glink12_off(g, p, mu, i));
+        const double2* s8 = u8t + ((((size_t)p * g.nch + (size_t)(i >> 6)) * 4 + mu) * 4) * 64 + (i & 63);
+#pragma unroll
+        for (int e = 0; e < 4; e++) w[e] = ld(s8 + (size_t)e * 64);
+        double tau, big;
+        link8_decode(w, u, phi, tau, big);
+        tg_row2(u);
+#pragma unroll
+        for (int e = 0; e < 9; e++) {
+            const double d1 = fabs(u[e].re - ref[e].re), d2 = fabs(u[e].im - ref[e].im);
+            dev = (d1 <= 1e300 && d2 <= 1e300) ? fmax(dev, fmax(d1, d2)) : 1e300;
+        }
+        if (!(big <= 1e30)) dev = 1e300;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) dev = fmax(dev, __shfl_down(dev, off, 64));
+    if ((threadIdx.x & 63) == 0 && dev > 0.0) atomicMax(maxdev, (unsigned long long)__double_as_longlong(dev));
+}
+// behind gauge_ensure_tgauge's 12-real copy: data8t and its measured deviation.  A failed allocation is no error: no copy, tgauge8_dev stays 1e300, the solve reads 12 reals
+static int gauge_build_tgauge8(lqcd_gauge_s* g) {
+    lqcd_ctx_s* c = g->ctx;
+    g->tgauge8_dev = 1e300;
+    g->version8t = g->version;
+    g->tgauge8_built = true;
+    if (!g->tgauge_ok) return LQCD_OK;
+    if (!g->data8t && hipMalloc((void**)&g->data8t, (size_t)2 * c->geom.nch * 16 * 64 * sizeof(double2)) != hipSuccess) { (void)hipGetLastError(); g->data8t = nullptr; return LQCD_OK; }
+    unsigned long long* d_dev = (unsigned long long*)(c->d_scal + SCAL_DOUBLES - 9);
+    HIPCHK(hipMemsetAsync(d_dev, 0, sizeof(unsigned long long), c->stream));
+    const dim3 grid((c->geom.Vh + 255) / 256, 8), block(256);
+    hipLaunchKernelGGL(tgauge8_encode, grid, block, 0, c->stream, c->geom, g->data12t, g->data8t);
+    hipLaunchKernelGGL(tgauge8_gate, grid, block, 0, c->stream, c->geom, g->data12t, g->data8t, d_dev);
+    HIPCHK(hipGetLastError());
+    unsigned long long bits = 0;
+    HIPCHK(hipMemcpyAsync(&bits, d_dev, sizeof(bits), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    memcpy(&g->tgauge8_dev, &bits, sizeof(double));
+    return LQCD_OK;
+}
+
+int gauge_ensure_tgauge(lqcd_gauge_s* g, bool want8) {
     LQCHK(gauge_ensure_recon12(g));
-    if (g->version12t == g->version && g->data12t && g->gfix) return LQCD_OK;
+    if (g->version12t == g->version && g->data12t && g->gfix) return (want8 && !(g->tgauge8_built && g->version8t == g->version)) ? gauge_build_tgauge8(g) : LQCD_OK;
     lqcd_ctx_s* c = g->ctx;
     g->tgauge_ok = false;
     if (!g->recon_ok || c->geom.part[0] || c->geom.part[1] || c->geom.part[2] || c->geom.part[3] || c->geom.L[3] < 2) return LQCD_OK;
@@ -739,7 +835,9 @@ int gauge_ensure_tgauge(lqcd_gauge_s* g) {
     g->tgauge_ok = dev <= 1e-14;
     g->tgauge_dev = dev;
     g->version12t = g->version;
-    return LQCD_OK;
+    g->tgauge8_built = false;
+    g->tgauge8_dev = 1e300;
+    return want8 ? gauge_build_tgauge8(g) : LQCD_OK;
 }
 
 double2* spinor_block(lqcd_spinor_s* s, int p) {

@@ -205,6 +205,67 @@ template <int K> __device__ inline cd mul_ipow(cd a) {
     else if constexpr (k == 2) return mk(-a.re, -a.im);
     else return mk(a.im, -a.re);
 }
+
+#ifndef LQCD_F32
+// ---------------------------------------------------------------- 8-real links (temporal-gauge copy, lqcd_gauge_s::data8t)
+// Rows a, b of an SU(3) matrix from 8 reals, with no divisor that vanishes on the group away from two points of it:
+//   a, a unit vector of C^3 = a point of S^5 (Re a1, Re a2, Re a3, Im a1, Im a2 | Im a3), is its stereographic image X in R^5 from the pole Im a3 = 1:
+//   x_i = 2 X_i / (n + 1), Im a3 = (n - 1) / (n + 1), n = |X|^2;
+//   b = H (0, c1, c2)^T with H = 1 - tau v v^+ the Householder reflector of a (v = a + phi e1, phi = a1 / |a1|, tau = 1 / (1 + |a1|)) and (c1, c2) a unit vector
+//   of C^2, stored the same way as Y in R^3 from the pole Im c2 = 1.  With s = conj(a2) c1 + conj(a3) c2: b = (-phi s, c1 - tau a2 s, c2 - tau a3 s).
+// Words: (X1, X4) (X2, X5) (X3, Y3) (Y1, Y2) -- the images of a1, a2, (Re a3, Re c2), c1.  |a1| = 2 rho / (n + 1) with rho = |(X1, X4)|, phi = (X1 + i X4) / rho,
+// tau = (n + 1) / (n + 1 + 2 rho): one rsq (rho) and one rcp (of the product of the three denominators), each with two Newton steps -- to rounding, since an error of
+// phi's modulus is an error of b1.  Where rho^2 < 1e-280 (the stored words of a1 leave no phase) phi = 1 and rho = 0: any unit phi gives a frame, the encoder uses this one.
+__device__ inline void link8_sqrt_rsqrt(double x, double& g, double& y) {      // g = sqrt(x), y = 1 / sqrt(x); x normal and positive
+    const double y0 = __builtin_amdgcn_rsq(x);
+    g = x * y0;
+    double h = 0.5 * y0;
+    double r = fma(-h, g, 0.5);
+    g = fma(g, r, g); h = fma(h, r, h);
+    r = fma(-h, g, 0.5);
+    g = fma(g, r, g); h = fma(h, r, h);
+    y = h + h;
+}
+__device__ inline double link8_rcp(double p) {      // p normal, >= 1
+    double r = __builtin_amdgcn_rcp(p);
+    double e = fma(-p, r, 1.0);
+    r = fma(r, e, r);
+    e = fma(-p, r, 1.0);
+    return fma(r, e, r);
+}
+// w: the four stored words; u[0..5]: rows a, b (u[6..8] untouched: recon_row2 / tg_row2 rebuild row 2 as for the 12-real copy).  phi, tau: the frame the encoder projects
+// with; big = max(|X|^2, |Y|^2): beyond 1e30 the link sits on a pole of the chart and fails the gate.  The stencils use u alone
+__device__ inline void link8_decode(const cd (&w)[4], cd (&u)[9], cd& phi, double& tau, double& big) {
+    const double X1 = w[0].re, X4 = w[0].im, X2 = w[1].re, X5 = w[1].im, X3 = w[2].re, Y3 = w[2].im, Y1 = w[3].re, Y2 = w[3].im;
+    double r2 = X1 * X1; r2 = fma(X4, X4, r2);
+    double n = fma(X2, X2, r2); n = fma(X5, X5, n); n = fma(X3, X3, n);
+    double m = Y1 * Y1; m = fma(Y2, Y2, m); m = fma(Y3, Y3, m);
+    const bool tiny = r2 < 1e-280;
+    double g, y;
+    link8_sqrt_rsqrt(tiny ? 1.0 : r2, g, y);
+    const double rho = tiny ? 0.0 : g;
+    phi = mk(tiny ? 1.0 : X1 * y, tiny ? 0.0 : X4 * y);
+    const double d1 = n + 1.0, d2 = m + 1.0, d3 = fma(2.0, rho, d1), d12 = d1 * d2;
+    const double R = link8_rcp(d12 * d3);
+    const double t = R * d3;
+    const double ha = t * d2, hc = t * d1;      // 1 / d1, 1 / d2
+    const double ia = ha + ha, ic = hc + hc;
+    tau = (R * d12) * d1;                       // d1 / d3
+    big = n > m ? n : m;
+    const cd a2 = mk(X2 * ia, X5 * ia), a3 = mk(X3 * ia, (n - 1.0) * ha);
+    const cd c1 = mk(Y1 * ic, Y2 * ic), c2 = mk(Y3 * ic, (m - 1.0) * hc);
+    u[0] = mk(X1 * ia, X4 * ia); u[1] = a2; u[2] = a3;
+    cd s = mk(a2.re * c1.re, a2.re * c1.im);      // conj(a2) c1 + conj(a3) c2
+    s.re = fma(a2.im, c1.im, s.re); s.im = fma(-a2.im, c1.re, s.im);
+    cfma_conj(s, a3, c2);
+    const cd ts = mk(tau * s.re, tau * s.im);
+    u[3] = mk(fma(phi.im, s.im, -(phi.re * s.re)), -fma(phi.re, s.im, phi.im * s.re));
+    cd b2 = c1, b3 = c2;
+    cfma(b2, mk(-a2.re, -a2.im), ts);
+    cfma(b3, mk(-a3.re, -a3.im), ts);
+    u[4] = b2; u[5] = b3;
+}
+#endif
 }  // inline namespace
 
 // gamma_mu (mu = 0,1,2) has one entry per row: row a -> column PERM[mu][a], value i^GK[mu][a]  (SURVEY.md Appendix A);
@@ -548,6 +609,12 @@ struct Tunables {
                               // its stencils skip the time-like links below the seam.  0: off; 1 (default): beyond the cg_small regime (more than 1024 stencil workgroups);
                               // 2: whenever admissible (tests)
     int tgauge_active = 0;    // read-only: 1 if the last CG set up through cg_setup ran in temporal gauge
+    int cg_tgauge_recon = 8;  // reals per link the temporal-gauge CG reads: 12 (rows 0, 1) or 8 (lqcd_gauge_s::data8t, the chart of link8_decode; 64 B instead of 96 B per link).
+                              // 8 holds for a whole solve or not at all: residual-ring, Fused and DeferX forms, the 8-real copy built and inside its gate.  Unset, it applies beyond
+                              // 1024 stencil workgroups only (smaller lattices keep the bits of the 12-real solve)
+    int cg_tgauge_recon_set = 0;   // cg_tgauge_recon was set through lqcd_set_tunable
+    int tgauge_recon_active = 0;   // read-only: 8 or 12 if the last CG set up through cg_setup ran in temporal gauge (the link format of every stencil launch of it), else 0
+    int tgauge8_gate_e = 14;  // the 8-real copy is used when max |decode(encode(U')) - U'| <= 10^-e (14: the bound of the 12-real gate; larger values force the 12-real solve: tests)
     int cg_sweep_alt = 1;     // Wilson CG in temporal gauge (residual ring, Fused and DeferX forms): every D^+ launch of an iteration walks the (pass, t) slabs of the XCD tile
                               // sweep backwards (StencilCall::sweep_rev), so that it begins where the D before it ended and the D behind it begins where it ends -- the
                               // neighbour, link and centre streams of the first slabs of a launch are then what the launch before touched last.  Same sites, same
@@ -935,6 +1002,12 @@ struct lqcd_gauge_s {
     uint64_t version12t = 0;
     bool tgauge_ok = false;      // rows 0, 1 of every U' rebuild its row 2 to 1e-14 and every time-like U' below the seam is the unit matrix to 1e-14
     double tgauge_dev = 0.0;     // the larger of those two deviations
+    // 8-real form of the temporal-gauge copy (fields.hip gauge_ensure_tgauge, link8_decode below): [parity][chunk][mu][4][64], every link of data12t encoded, the time-like ones
+    // below the seam included (never read).  tgauge8_dev = max over all links and all nine entries of |decode(data8t) - U'| (1e300: a link on a pole of the chart, or no copy)
+    double2* data8t = nullptr;
+    uint64_t version8t = 0;
+    bool tgauge8_built = false;  // the encode + gate pass ran for version8t (a failed allocation counts: it is not tried again for this version)
+    double tgauge8_dev = 1e300;
     uint64_t unitary_version = 0;  // version of `data` whose links are all known to be on the group to rounding (generated on it, measured by the
                                    // 12-real pass, or projected by the link update): kernels may then rebuild row 2 instead of loading it
 };
@@ -1072,6 +1145,8 @@ struct StencilCall {
     const double2* gauge12 = nullptr;  // compressed links (fp64 build, Wilson r = 1 split kernel) or nullptr
     const double2* gauge12t = nullptr; // temporal-gauge copy of the 12-real links (lqcd_gauge_s::data12t; the Wilson CG on rotated vectors): read in place of gauge12; the
                                        // scalar-addressing kernel's TG instances skip the time-like links below the seam, every other 12-real kernel multiplies by their unit matrices
+    const double2* gauge8t = nullptr;  // beside gauge12t: the 8-real form of the same links (lqcd_gauge_s::data8t), read by the TG8 instances of the scalar-addressing kernel.  A call
+                                       // that carries it and does not reach such an instance is an error, never a 12-real launch (a CG runs on one link format throughout)
     const void* gauge16 = nullptr;     // prec == 2 only: the int16 fixed-point pair copy of the 12-real links (stencil_pair32.hip ldx16); the kernel then reads it instead of gauge12
     int gauge12_delta = 0;        // 1: gauge12 is the 8-word "12 + delta" copy (lqcd_gauge_s::data12d); only the scalar-addressing Wilson kernel reads it, every
                                   // other launch of the call falls back to the 18 stored reals
@@ -1145,7 +1220,7 @@ int flush_waiting_pack(lqcd_ctx_s* c);       // apply.hip
 int halo_schedule_settle(lqcd_op_s* op);   // partitioned context with halo_stream_mode = -1: run the one-off schedule timing now (apply.hip)
 int op_refresh_clover(lqcd_op_s* op);   // rebuilds A when the links moved; clover_version follows only a successful build
 void apply_bc(lqcd_ctx_s* c, const int bc[4]);
-int op_apply_async(lqcd_op_s* op, lqcd_spinor_s* out, lqcd_spinor_s* in, int dagger, double* norm_partial, const double* skip_flag = nullptr, const double2* gauge12t = nullptr);
+int op_apply_async(lqcd_op_s* op, lqcd_spinor_s* out, lqcd_spinor_s* in, int dagger, double* norm_partial, const double* skip_flag = nullptr, const double2* gauge12t = nullptr, const double2* gauge8t = nullptr);
 int cg_run(lqcd_op_s* op, lqcd_spinor_s* x, lqcd_spinor_s* b, double eps, int maxiter, bool fixed, int* iters, double* final_rr);
 bool any_partitioned(lqcd_ctx_s* c);
 bool halo_fold_applies(lqcd_ctx_s* c, int kind, double r, int parity_mode, int prec, bool clover);   // the folded one-stream schedule runs for such a call (stencil.hip)
@@ -1190,7 +1265,8 @@ int clover_force(lqcd_ctx_s* c, const lqcd_gauge_s* U, lqcd_gauge_s* out, lqcd_s
 double2* spinor_block(lqcd_spinor_s* s, int p);
 int gauge_ensure_recon12(lqcd_gauge_s* g);   // (re)builds the 12-real copy if the field changed; sets g->recon_ok
 int gauge_ensure_recon12d(lqcd_gauge_s* g);  // (re)builds the "12 + delta" copy; sets g->delta_ok
-int gauge_ensure_tgauge(lqcd_gauge_s* g);    // (re)builds G and the temporal-gauge copy of the 12-real links if the field changed; sets g->tgauge_ok
+int gauge_ensure_tgauge(lqcd_gauge_s* g, bool want8 = false);    // (re)builds G and the temporal-gauge copy of the 12-real links if the field changed; sets g->tgauge_ok.  want8:
+                                             // behind it the 8-real copy and its measured deviation g->tgauge8_dev
 int spinor_gauge_rotate(lqcd_ctx_s* c, const double2* gfix, double2* dst, const double2* src, int adjoint);   // cg.hip: dst = G src / G^+ src on a full Wilson field (dst may be src)
 bool stencil_sdir_applies(lqcd_ctx_s* c, int kind, double r, bool clover);     // stencil.hip: a full-lattice fp64 application takes the scalar-addressing Wilson kernel (upd_src / upd_rec exist there)
 int stencil_sweep_slabs(lqcd_ctx_s* c);      // stencil.hip: slabs (pass, t) of a full-lattice launch of the scalar-addressing kernel, 0 if the map does not give any

@@ -42,6 +42,7 @@ struct CgWork {
     // the rotated links; cg_finish rotates x back
     bool tgauge = false;
     const double2* links_t = nullptr;      // lqcd_gauge_s::data12t of the field version the solve was set up on
+    const double2* links_t8 = nullptr;     // lqcd_gauge_s::data8t: the solve reads 8 reals per link, every stencil launch of it, set-up included; nullptr: 12
     const double2* gfix = nullptr;
     uint64_t gauge_version = 0;
     // alternating sweep (decided once in cg_setup from the tunable cg_sweep_alt, temporal gauge only): every D^+ launch of an iteration sets StencilCall::sweep_rev

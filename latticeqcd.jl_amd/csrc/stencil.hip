@@ -534,18 +534,19 @@ __device__ inline void pipe_wave(const PipeArgs& a, real2 (*part)[12][64], volat
     constexpr int FF = MU == 3 ? (SF > 0 ? 6 : 0) : 0;         // first component of the forward / backward hop's rows
     constexpr int FB = MU == 3 ? (SF > 0 ? 0 : 6) : 0;
     constexpr int NL = R12 ? 6 : 9;
+    constexpr int LF = R12 ? 12 : 18;                          // reals per link (load_link_f / finish_link_f)
     const int nper = a.nvirt >> 3;
     const size_t gpar = (size_t)a.nch * 4 * NL * 64;           // elements of one parity block of the gauge field
     PipeSite s = pipe_site<MU, NL>(a, vb, lane);
     cd sF[NS], uF[9];
     load_comps12<FF, NS, false>(sF, boff(s.p ? a.in[0] : a.in[1], s.nf));
-    load_link_any<R12, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64);
+    load_link_f<LF, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64);
     for (;;) {
         cd acc[12], chi0[3], chi1[3], h0[3], h1[3];
 #pragma unroll
         for (int j = 0; j < 12; j++) acc[j] = mk(0.0, 0.0);
         // forward hop: its operands were issued one stage ago (prologue, or in front of the previous chunk's second barrier)
-        finish_link<R12>(uF);
+        finish_link_f<LF>(uF);
         project_regs<MU, SF>(h0, h1, sF);
         pipe_sign(h0, h1, s.sf);
         su3_mv<false>(chi0, uF, h0);
@@ -566,7 +567,7 @@ __device__ inline void pipe_wave(const PipeArgs& a, real2 (*part)[12][64], volat
         // backward hop's operands, into the registers the forward operands occupied
         cd sB[NS], uB[9];
         load_comps12<FB, NS, false>(sB, boff(s.p ? a.in[0] : a.in[1], s.nb));
-        load_link_any<R12, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
+        load_link_f<LF, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
         // the NEXT chunk: one lane of the x wave pulls it from the queue now -- as late as its answer can still arrive for free (it returns
         // with the loads above).  Pulling earlier lets the order in which chunks are handed out drift away from the order in which their
         // loads are issued, and the L2 hits of the sweep live on that order (profiles/r03_pipe_lookahead.log).
@@ -575,7 +576,7 @@ __device__ inline void pipe_wave(const PipeArgs& a, real2 (*part)[12][64], volat
             if (a.ctr && lane == 0 && tries < 8) tick = __hip_atomic_fetch_add(a.ctr + 32 * q, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         __builtin_amdgcn_sched_barrier(0);
-        finish_link<R12>(uB);
+        finish_link_f<LF>(uB);
         project_regs<MU, -SF>(h0, h1, sB);
         pipe_sign(h0, h1, s.sb);
         su3_mv<true>(chi0, uB, h0);
@@ -616,7 +617,7 @@ __device__ inline void pipe_wave(const PipeArgs& a, real2 (*part)[12][64], volat
 #endif
 #if !LQCD_PIPE_NOPF
         load_comps12<FF, NS, false>(sF, boff(sn.p ? a.in[0] : a.in[1], sn.nf));
-        load_link_any<R12, false>(uF, boff(a.gauge + (sn.p ? gpar : 0), sn.uf), 64);
+        load_link_f<LF, false>(uF, boff(a.gauge + (sn.p ? gpar : 0), sn.uf), 64);
 #endif
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // LDS writes done; NO vmcnt wait: the loads above stay in flight
@@ -648,7 +649,7 @@ __device__ inline void pipe_wave(const PipeArgs& a, real2 (*part)[12][64], volat
         s = sn;
 #if LQCD_PIPE_NOPF      // experiment: persistent only, the forward operands are issued at the top of the chunk like variant 1
         load_comps12<FF, NS, false>(sF, boff(s.p ? a.in[0] : a.in[1], s.nf));
-        load_link_any<R12, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64);
+        load_link_f<LF, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64);
 #endif
     }
 }
@@ -805,7 +806,9 @@ __host__ __device__ constexpr bool sdir_keep_instance(bool r12, bool delta) { re
 // TG (plain fp64 12-real instances only): the links are the temporal-gauge copy (lqcd_gauge_s::data12t) -- a time-like link is the unit matrix unless its hop crosses
 // the seam t = T - 1 -> 0, which is what s.wf / s.wb say for MU = 3 (wave-uniform): the t wave loads no link and skips the two SU(3) products and the row-2
 // rebuild everywhere else.  The boundary sign stays with pipe_sign.
-template <int MU, bool DAG, bool R12, bool NTB, bool DOT = false, bool DELTA = false, bool DW5 = false, bool FOLD = false, bool CINV = false, bool TG = false>
+// TG8 (with TG and R12): the links are the 8-real form of that copy (lqcd_gauge_s::data8t, four words per link): load_link_f loads them, finish_link_f decodes rows 0, 1
+// (link8_decode) and rebuilds row 2; nothing behind su3_mv's nine entries changes, and the t wave decodes only under the scalar branches of its seam hops.
+template <int MU, bool DAG, bool R12, bool NTB, bool DOT = false, bool DELTA = false, bool DW5 = false, bool FOLD = false, bool CINV = false, bool TG = false, bool TG8 = false>
 __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int lane, real al_upd, real& nrm, real& dre, real& dim, int vb, real& dre2, real& dim2, int keep = -1) {
     // DW5: this workgroup's slice s5 of the five-dimensional fields; block ids keep their XCD (b & 7) and the L5 slices of a chunk follow each other on it, so the
     // links of the chunk are fetched from the fabric once and hit the XCD's L2 for the other slices
@@ -828,7 +831,8 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
     constexpr int NS = MU == 3 ? 6 : 12;
     constexpr int FF = MU == 3 ? (SF > 0 ? 6 : 0) : 0;
     constexpr int FB = MU == 3 ? (SF > 0 ? 0 : 6) : 0;
-    constexpr int NL = DELTA ? 8 : (R12 ? 6 : 9);      // 16-byte words per link: 18 reals | rows 0, 1 | rows 0, 1 + the fp32 deviation of row 2 (add_delta_row2)
+    constexpr int NL = TG8 ? 4 : DELTA ? 8 : (R12 ? 6 : 9);      // 16-byte words per link: 8 reals (TG8) | 18 reals | rows 0, 1 | rows 0, 1 + the fp32 deviation of row 2 (add_delta_row2)
+    constexpr int LF = TG8 ? 8 : (R12 ? 12 : 18);                // reals per link that load_link_f / finish_link_f turn into the nine entries
 #ifdef LQCD_F32
     constexpr bool LATE_R = false;
 #else
@@ -890,16 +894,16 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
     {   // both hops' operands in flight at once (fp32 build: half-size registers leave the room at 4 waves per SIMD; twice the bytes in flight per wave)
         cd sF[NS], uF[9], sB[NS], uB[9];
         load_comps12<FF, NS, false>(sF, boff(s.p ? a.in[0] : a.in[1], s.nf));
-        load_link_any<R12, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64);
+        load_link_f<LF, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64);
         load_comps12<FB, NS, false>(sB, boff(s.p ? a.in[0] : a.in[1], s.nb));
-        load_link_any<R12, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
-        finish_link<R12>(uF);
+        load_link_f<LF, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
+        finish_link_f<LF>(uF);
         project_regs<MU, SF>(h0, h1, sF);
         pipe_sign(h0, h1, s.sf);
         su3_mv<false>(chi0, uF, h0);
         su3_mv<false>(chi1, uF, h1);
         reconstruct<MU, SF>(acc, chi0, chi1);
-        finish_link<R12>(uB);
+        finish_link_f<LF>(uB);
         project_regs<MU, -SF>(h0, h1, sB);
         pipe_sign(h0, h1, s.sb);
         su3_mv<true>(chi0, uB, h0);
@@ -926,7 +930,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
             {
                 cd sF[12], uF[9], dF[2];
                 if (row == 3) load_comps12<0, 12, false>(sF, boff(s.p ? a.in[0] : a.in[1], s.nf));      // row 0 of the next chunk in y (the wrap: of the plane's first)
-                load_link_any<R12, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64);
+                load_link_f<LF, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64);
                 if constexpr (DELTA) { dF[0] = ld(boff(a.gauge + (s.p ? gpar : 0), s.uf) + 6 * 64); dF[1] = ld(boff(a.gauge + (s.p ? gpar : 0), s.uf) + 7 * 64); }
                 asm volatile("" ::: "memory");
                 __builtin_amdgcn_s_barrier();      // the x wave's chunk is in part[1] (this wave has written no LDS: nothing to wait for in front)
@@ -935,7 +939,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
 #pragma unroll
                     for (int j = 0; j < 12; j++) sF[j] = ld(&part[1][j][lane + 16]);
                 }
-                finish_link<R12>(uF);
+                finish_link_f<LF>(uF);
                 if constexpr (DELTA) add_delta_row2(uF, dF);
                 project_regs<MU, SF>(h0, h1, sF);
                 pipe_sign(h0, h1, s.sf);
@@ -947,7 +951,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
             {
                 cd sB[12], uB[9], dB[2];
                 if (row == 0) load_comps12<0, 12, false>(sB, boff(s.p ? a.in[0] : a.in[1], s.nb));      // row 3 of the previous chunk in y
-                load_link_any<R12, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
+                load_link_f<LF, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
                 if constexpr (DELTA) {
                     const real2* db = boff(a.gauge + (s.p ? 0 : gpar), s.ub);
                     dB[0] = NTB ? ld_nt(db + 6 * 64) : ld(db + 6 * 64);
@@ -957,7 +961,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
 #pragma unroll
                     for (int j = 0; j < 12; j++) sB[j] = ld(&part[1][j][lane - 16]);
                 }
-                finish_link<R12>(uB);
+                finish_link_f<LF>(uB);
                 if constexpr (DELTA) add_delta_row2(uB, dB);
                 project_regs<MU, -SF>(h0, h1, sB);
                 pipe_sign(h0, h1, s.sb);
@@ -976,7 +980,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
             {
                 cd sX[12], uF[9], dF[2];
                 load_comps12<0, 12, false>(sX, boff(s.p ? a.in[0] : a.in[1], s.own));
-                load_link_any<R12, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64);
+                load_link_f<LF, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64);
                 if constexpr (DELTA) { dF[0] = ld(boff(a.gauge + (s.p ? gpar : 0), s.uf) + 6 * 64); dF[1] = ld(boff(a.gauge + (s.p ? gpar : 0), s.uf) + 7 * 64); }
                 if (ysh) {      // y-share: the raw chunk to the y wave's slab, first of all -- the other three waves are held at the barrier until it is there
 #pragma unroll
@@ -997,7 +1001,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
                 const int lf = (int)(s.nf >> 4) & 63;      // the lane that holds the forward neighbour: i or i + 1, the wrap inside the row of 16
 #pragma unroll
                 for (int c = 0; c < 3; c++) { h0[c] = ld(&part[0][c][lf]); h1[c] = ld(&part[0][3 + c][lf]); }
-                finish_link<R12>(uF);
+                finish_link_f<LF>(uF);
                 if constexpr (DELTA) add_delta_row2(uF, dF);
                 pipe_sign(h0, h1, s.sf);
                 su3_mv<false>(chi0, uF, h0);
@@ -1007,7 +1011,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
             __builtin_amdgcn_sched_barrier(0);
             {
                 cd uB[9], dB[2];
-                load_link_any<R12, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
+                load_link_f<LF, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
                 if constexpr (DELTA) {
                     const real2* db = boff(a.gauge + (s.p ? 0 : gpar), s.ub);
                     dB[0] = NTB ? ld_nt(db + 6 * 64) : ld(db + 6 * 64);
@@ -1016,7 +1020,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
                 const int lb = (int)(s.nb >> 4) & 63;      // i - 1 or i
 #pragma unroll
                 for (int c = 0; c < 3; c++) { h0[c] = ld(&part[0][6 + c][lb]); h1[c] = ld(&part[0][9 + c][lb]); }
-                finish_link<R12>(uB);
+                finish_link_f<LF>(uB);
                 if constexpr (DELTA) add_delta_row2(uB, dB);
                 pipe_sign(h0, h1, s.sb);
                 su3_mv<true>(chi0, uB, h0);
@@ -1030,8 +1034,8 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
         cd sF[NS], uF[9], dF[2];
         if constexpr (FOLD && MU >= 1) fold_load_spinor<MU, NS, FF>(sF, boff(s.p ? a.in[0] : a.in[1], s.nf), a.gh_f[MU] + gslot, a.Fh[MU], gF);
         else load_comps12<FF, NS, false>(sF, boff(s.p ? a.in[0] : a.in[1], s.nf));
-        if constexpr (TG && MU == 3) { if (s.wf) load_link_any<R12, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64); }      // (scalar branch)
-        else load_link_any<R12, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64);
+        if constexpr (TG && MU == 3) { if (s.wf) load_link_f<LF, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64); }      // (scalar branch)
+        else load_link_f<LF, false>(uF, boff(a.gauge + (s.p ? gpar : 0), s.uf), 64);
         if constexpr (DELTA) { dF[0] = ld(boff(a.gauge + (s.p ? gpar : 0), s.uf) + 6 * 64); dF[1] = ld(boff(a.gauge + (s.p ? gpar : 0), s.uf) + 7 * 64); }
         if constexpr (YSI && MU >= 2) {      // y-share: the z and t waves arrive at its barrier with their forward operands in flight (no LDS access of theirs to order, no wait on a load)
             if (ysh) {
@@ -1053,7 +1057,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
                                                  (__attribute__((address_space(3))) void*)(&part[MU][j][0]), 16, 0, 0);
         }
 #endif
-        if constexpr (!(TG && MU == 3)) finish_link<R12>(uF);
+        if constexpr (!(TG && MU == 3)) finish_link_f<LF>(uF);
 #ifndef LQCD_F32
         if constexpr (DELTA) add_delta_row2(uF, dF);
 #endif
@@ -1061,7 +1065,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
         pipe_sign(h0, h1, sgF);
         if constexpr (TG && MU == 3) {
             if (s.wf) {
-                finish_link<R12>(uF);
+                finish_link_f<LF>(uF);
                 su3_mv<false>(chi0, uF, h0);
                 su3_mv<false>(chi1, uF, h1);
             } else {
@@ -1078,7 +1082,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
     {
         cd sB[NS], uB[9], dB[2];
 #if LQCD_SDIR_GLDS
-        load_link_any<R12, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
+        load_link_f<LF, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the LDS copies (issued long ago) and the link
 #pragma unroll
         for (int j = 0; j < NS; j++) sB[j] = ld(&part[MU][j][lane]);
@@ -1086,15 +1090,15 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
         if constexpr (FOLD && MU >= 2) {
             fold_load_spinor<MU, NS, FB>(sB, boff(s.p ? a.in[0] : a.in[1], s.nb), a.gh_b[MU] + gslot, a.Fh[MU], gB);
             if (gB) fold_unit_link<MU, R12>(uB, true);      // (scalar branch: the ghost is U^+ P psi already, no link is read)
-            else load_link_any<R12, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
+            else load_link_f<LF, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
         } else if constexpr (FOLD && MU == 1) {
             fold_load_spinor<MU, NS, FB>(sB, boff(s.p ? a.in[0] : a.in[1], s.nb), a.gh_b[MU] + gslot, a.Fh[MU], gB);
-            load_link_any<R12, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
+            load_link_f<LF, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
             fold_unit_link<MU, R12>(uB, gB);
         } else {
             load_comps12<FB, NS, false>(sB, boff(s.p ? a.in[0] : a.in[1], s.nb));
-            if constexpr (TG && MU == 3) { if (s.wb) load_link_any<R12, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64); }
-            else load_link_any<R12, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
+            if constexpr (TG && MU == 3) { if (s.wb) load_link_f<LF, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64); }
+            else load_link_f<LF, NTB>(uB, boff(a.gauge + (s.p ? 0 : gpar), s.ub), 64);
         }
 #endif
         if constexpr (DELTA) {
@@ -1102,7 +1106,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
             dB[0] = NTB ? ld_nt(db + 6 * 64) : ld(db + 6 * 64);
             dB[1] = NTB ? ld_nt(db + 7 * 64) : ld(db + 7 * 64);
         }
-        if constexpr (!(TG && MU == 3)) finish_link<R12>(uB);
+        if constexpr (!(TG && MU == 3)) finish_link_f<LF>(uB);
 #ifndef LQCD_F32
         if constexpr (DELTA) add_delta_row2(uB, dB);
 #endif
@@ -1110,7 +1114,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
         pipe_sign(h0, h1, sgB);
         if constexpr (TG && MU == 3) {
             if (s.wb) {
-                finish_link<R12>(uB);
+                finish_link_f<LF>(uB);
                 su3_mv<true>(chi0, uB, h0);
                 su3_mv<true>(chi1, uB, h1);
             } else {
@@ -1255,7 +1259,7 @@ __device__ inline void sdir_wave(const PipeArgs& a_, real2 (*part)[12][64], int 
 }
 
 // the workgroup of the scalar-addressing kernel; its two entry points (wilson_dirsplit_s and the temporal-gauge wilson_dirsplit_s_tg) own the LDS
-template <bool DAG, bool R12, bool NTB, bool DOT, bool DELTA, bool DW5, bool FOLD, bool CINV, bool TG>
+template <bool DAG, bool R12, bool NTB, bool DOT, bool DELTA, bool DW5, bool FOLD, bool CINV, bool TG, bool TG8 = false>
 __device__ __forceinline__ void dirsplit_s_block(const PipeArgs& a, real2 (*part)[12][64], double* red) {
     if ((a.upd_scal && a.upd_scal[S_DONE] != 0.0) || (a.skip && a.skip[S_DONE] != 0.0)) {
         if (a.scal_w && blockIdx.x == 0 && threadIdx.x == 0) a.scal_w[S_XDONE] = 1.0;
@@ -1308,10 +1312,10 @@ __device__ __forceinline__ void dirsplit_s_block(const PipeArgs& a, real2 (*part
     const int lane = threadIdx.x & 63;
     real nrm = 0.0, dre = 0.0, dim = 0.0, dre2 = 0.0, dim2 = 0.0;
     switch (w) {
-    case 0: sdir_wave<0, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2, keep); break;
-    case 1: sdir_wave<1, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2, keep); break;
-    case 2: sdir_wave<2, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2, keep); break;
-    default: sdir_wave<3, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2, keep); break;
+    case 0: sdir_wave<0, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG, TG8>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2, keep); break;
+    case 1: sdir_wave<1, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG, TG8>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2, keep); break;
+    case 2: sdir_wave<2, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG, TG8>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2, keep); break;
+    default: sdir_wave<3, DAG, R12, NTB, DOT, DELTA, DW5, FOLD, CINV, TG, TG8>(a, part, lane, al_upd, nrm, dre, dim, vb, dre2, dim2, keep); break;
     }
     if constexpr (DOT) {                // three sums per workgroup, the order of wilson_dirsplit's dot epilogue; five with a second inner product (dot_z2)
         const bool five = a.dotz2[0] != nullptr || a.dotz2[1] != nullptr;
@@ -1349,6 +1353,13 @@ __global__ __launch_bounds__(256, 3) void wilson_dirsplit_s_tg(PipeArgs a) {
     __shared__ real2 part[4][12][64];
     __shared__ double red[4];
     dirsplit_s_block<DAG, true, NTB, false, false, false, false, false, true>(a, part, red);
+}
+// the same instance on the 8-real form of that copy (sdir_wave, TG8; PipeArgs::gauge is lqcd_gauge_s::data8t): 64 instead of 96 B per link and lane
+template <bool DAG, bool NTB>
+__global__ __launch_bounds__(256, 3) void wilson_dirsplit_s_tg8(PipeArgs a) {
+    __shared__ real2 part[4][12][64];
+    __shared__ double red[4];
+    dirsplit_s_block<DAG, true, NTB, false, false, false, false, false, true, true>(a, part, red);
 }
 #endif
 
@@ -2144,6 +2155,11 @@ int launch_stencil_interior(lqcd_ctx_s* c, const StencilCall& s) {
         set_error("stencil: temporal-gauge links are read by the 12-real Wilson r = 1 direction-split kernels only");
         return LQCD_ERR_UNSUPPORTED;
     }
+    if (s.gauge8t) {      // the 8-real links have one reader, the TG8 instances: a call that would end anywhere else is refused here (the conditions of that branch below)
+        const bool ok = !kF32Build && s.gauge12t && s.prec == 0 && use_dirsplit(c, s.kind, s.r) && !s.fold && !s.dot_partial && !s.clover_on_hop && !s.clover && !s.alpha_partials &&
+                        s.dw_ls <= 1 && !s.gauge12_delta && c->tun.dslash_pipe == 2 && c->geom.L[3] >= 2 && wilson_pipe_applies(c, s.kind, s.r, s.parity_mode, false);
+        if (!ok) { set_error("stencil: 8-real temporal-gauge links are read by the TG8 instances of the scalar-addressing Wilson kernel only"); return LQCD_ERR_UNSUPPORTED; }
+    }
     if (s.upd_rec || s.upd_src[0] || s.upd_src[1]) {      // the epilogues of the residual-ring CG exist in the scalar-addressing kernel alone (cg.hip asks stencil_sdir_applies first)
         const bool ok = !kF32Build && s.prec == 0 && s.upd_scal && s.upd[0] && s.upd[1] && !s.clover && !s.clover_on_hop && !s.dot_partial && !s.alpha_partials && s.dw_ls <= 1 && !s.fold &&
                         !s.scal_w && (s.gauge12 || s.gauge12t || c->tun.dslash_s18) && stencil_sdir_applies(c, s.kind, s.r, false);
@@ -2281,11 +2297,18 @@ int launch_stencil_interior(lqcd_ctx_s* c, const StencilCall& s) {
 #ifndef LQCD_F32
 #define LQ_TG(D) do { if (ntb) hipLaunchKernelGGL((wilson_dirsplit_s_tg<D, true>), pg, pb, 0, c->stream, a); \
                       else hipLaunchKernelGGL((wilson_dirsplit_s_tg<D, false>), pg, pb, 0, c->stream, a); } while (0)
+#define LQ_TG8(D) do { if (ntb) hipLaunchKernelGGL((wilson_dirsplit_s_tg8<D, true>), pg, pb, 0, c->stream, a); \
+                       else hipLaunchKernelGGL((wilson_dirsplit_s_tg8<D, false>), pg, pb, 0, c->stream, a); } while (0)
+            if (s.gauge12t && s.gauge8t && !persist && k.g.L[3] >= 2) {      // ... in their 8-real form
+                a.gauge = (const real2*)s.gauge8t;
+                if (s.dagger) LQ_TG8(true); else LQ_TG8(false);
+            } else
             if (s.gauge12t && !persist && k.g.L[3] >= 2) { if (s.dagger) LQ_TG(true); else LQ_TG(false); }      // temporal-gauge links: the t wave skips the unit links
             else
 #endif
             if (k.gauge12) { if (s.dagger) LQ_PIPE(true, true); else LQ_PIPE(false, true); }
             else { if (s.dagger) LQ_PIPE(true, false); else LQ_PIPE(false, false); }
+#undef LQ_TG8
 #undef LQ_TG
 #undef LQ_PIPE
             }

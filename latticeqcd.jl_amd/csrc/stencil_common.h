@@ -544,6 +544,30 @@ __device__ inline void load_link_any(cd (&u)[9], const real2* __restrict__ U, in
     load_link_raw<R12, NT>(u, U, Us);
 }
 
+// the link of the scalar-addressing kernel by format LF (reals per link: 18, 12, or 8 -- the temporal-gauge chart of link8_decode, fp64 build): the loads, and what turns
+// them into the nine entries su3_mv takes.  18 and 12 are load_link_any / finish_link unchanged
+template <int LF, bool NT>
+__device__ inline void load_link_f(cd (&u)[9], const real2* __restrict__ U, int Us) {
+    if constexpr (LF == 8) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) u[j] = NT ? ld_nt(U + (size_t)j * 64) : ld(U + (size_t)j * 64);
+    } else load_link_any<LF == 12, NT>(u, U, Us);
+}
+template <int LF>
+__device__ inline void finish_link_f(cd (&u)[9]) {
+#ifndef LQCD_F32
+    if constexpr (LF == 8) {
+        const cd w[4] = {u[0], u[1], u[2], u[3]};
+        cd phi;
+        double tau, big;
+        link8_decode(w, u, phi, tau, big);
+        recon_row2(u);
+        return;
+    }
+#endif
+    finish_link<LF == 12>(u);
+}
+
 // pack the faces a finished site lies on, from its 12 components in registers, for an application with dagger flag `dag`: the arithmetic of
 // wilson_pack_dir (lower face: P psi -> send_bwd; upper face: U^+ P psi -> send_fwd), so a prepacked application sees the same bits
 template <int NU>

@@ -469,6 +469,14 @@ def unitarity_deviation(U):
     return d.value
 
 
+def tgauge8_deviation(U):
+    """max |decode(encode(U')) - U'| over all entries of all links of the temporal-gauge copy (the gate of the 8-real temporal-gauge CG, tunable cg_tgauge_recon);
+    1e300: a link on a pole of the chart, or no copy.  Diagnostic, no reference counterpart."""
+    d = C.c_double(0)
+    check(_l.lib().lqcd_gauge_tgauge8_deviation(U._h, C.byref(d)))
+    return d.value
+
+
 # ------------------------------------------------------------------------------------ fermion fields
 class Fermionfields:
     """A pseudofermion field.  kind = DOMAINWALL: L5 Wilson fields in one allocation; `x.w[i5]` (the reference's name for a slice) is a Wilson field that
