@@ -147,7 +147,9 @@ int lqcd_ctx_sync(lqcd_ctx_t ctx);
  * interior -> exterior in order on one stream: no overlap and no cross-queue join, the faster one when the exchange is short), halo_tuned_us0..3 (read-only: the
  * times that choice was made from), halo_fuse (bit 1 [default 2]: the
  * exterior of D p packs the faces D^+ needs and the CG update packs the new search direction -- no separate pack launches; bit 0: the exterior's last
- * block sums the |.|^2 partials -- measured slower, off), staple_recon (1 [default]: the staple sweep reads two rows of links known to be on the group);
+ * block sums the |.|^2 partials -- measured slower, off), staple_recon (1 [default]: the staple sweep reads two rows of links known to be on the group;
+ * read-only staple_form_active: the form the last staple sweep took -- 0 generic kernel on 18 reals, 1 generic kernel on two rows, 2 the tile form of staple_tile,
+ * 3 the partitioned instance, -1 none has run on this context);
  * round 4: gauge_delta (1 [default]: a field that fails the 12-real gate but lies within 1e-9 of the group -- the reference's text / ILDG configurations -- is read by the
  * scalar-addressing Wilson kernel as rows 0, 1 in fp64 + the fp32 deviation of row 2, 128 B per link; results equal the 18-real kernel's to fp64 rounding; recon_active reads 2),
  * dslash_s18 (1 [default]: the scalar-addressing kernel also on the 18 stored reals), bicg_fused (even-odd BiCGStab of the Wilson / Wilson-clover operator: 2 inner

@@ -595,6 +595,9 @@ struct Tunables {
     int staple_recon = 1;     // staple sweep on a field whose links are known to be on the group: rows 0, 1 are loaded, row 2 is rebuilt (2/3 of the L2 -> L1 bytes)
     int staple_tile = 1;      // staple sweep (single GPU, links on the group, chunks of whole x-rows): the links of both parities of a chunk sit in LDS and every neighbour link
                               // inside that (x, y) tile is read from there (staple.hip gauge_force_kernel_tile); 0: every neighbour link through the L1 / L2 path
+    int staple_form_active = -1;  // read-only: the form of the last staple sweep (staple.hip launch_staple_sweep, launch_sweep_expu, flow_stage: force, momentum update, merged momentum +
+                              // link update, flow stage): 0 = generic kernel with 18-real loads, 1 = generic kernel with two-row loads, 2 = tile form, 3 = the partitioned instance;
+                              // -1: no sweep has run on this context
     int md_remap = 1;         // staple sweep: workgroups follow the Dslash kernels' XCD-aware tile sweep (0: plain chunk order)
     int cg_defer_x = 1;       // fused CG: 2 = x is updated every SECOND iteration with both search directions (x += a_k p_k + a_{k+1} p_{k+1}, p ping-pongs
                               // between two buffers): 9 instead of 10 spinor passes per iteration on average, identical iterates; K = 3..8 (round 5; 288 GB of HBM make

@@ -465,6 +465,8 @@ static int launch_staple_faces(lqcd_ctx_s* c, const GFArgs& k) {
 }
 static int launch_staple_sweep(lqcd_ctx_s* c, const GFArgs& k, bool fuse, bool two_rows) {
     const dim3 grid(2 * c->geom.nch);
+    // read-out for the tests (the same conditions as the dispatch below; a single-direction sweep has no tile form and loads two rows only where it is fused)
+    c->tun.staple_form_active = any_partitioned(c) ? 3 : k.mu_only >= 0 ? (fuse && two_rows ? 1 : 0) : !two_rows ? 0 : staple_tile_ok(c) ? 2 : 1;
     if (any_partitioned(c)) {       // the instance with the ghost-link / received-staple branches
         if (k.mu_only >= 0 && fuse) hipLaunchKernelGGL(gauge_force_kernel_part<3>, grid, dim3(64), 0, c->stream, k);
         else if (k.mu_only >= 0) hipLaunchKernelGGL(gauge_force_kernel_part<2>, grid, dim3(64), 0, c->stream, k);
@@ -548,6 +550,7 @@ static int spare_links(lqcd_ctx_s* c, const lqcd_gauge_s* U) {
 template <bool FLOW>
 static void launch_sweep_expu(lqcd_ctx_s* c, const GFArgs& k, bool two_rows) {
     const dim3 grid(2 * c->geom.nch);
+    c->tun.staple_form_active = !two_rows ? 0 : staple_tile_ok(c) ? 2 : 1;
     if (two_rows && staple_tile_ok(c)) hipLaunchKernelGGL((gauge_force_kernel_tile<1, true, FLOW>), grid, dim3(256), 0, c->stream, k);
     else if (two_rows) hipLaunchKernelGGL((gauge_force_kernel<1, false, true, true, FLOW>), grid, dim3(256), 0, c->stream, k);
     else hipLaunchKernelGGL((gauge_force_kernel<1, false, false, true, FLOW>), grid, dim3(256), 0, c->stream, k);
@@ -600,6 +603,7 @@ int flow_stage(lqcd_gauge_s* U, double2* X, double xscale, double factor, bool x
     k.out = X;
     k.xscale = xscale; k.xread = xread ? 1 : 0;
     LQCHK(staple_halo_lower(c, k));
+    c->tun.staple_form_active = 3;
     hipLaunchKernelGGL(gauge_force_kernel_part<4>, dim3(2 * c->geom.nch), dim3(256), 0, c->stream, k);
     HIPCHK(hipGetLastError());
     LQCHK(link_exp_update_enqueue(U, 1.0, X, reunit != 0, notproj));

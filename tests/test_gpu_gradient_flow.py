@@ -148,8 +148,10 @@ def test_rccl_self_partition_equals_the_single_domain_run(gpu, orc, tmp_path):
         lat = lq.Lattice(L)
         lat.comm_init(lq.comm_unique_id())
         U = lq.Gaugefields(lat).upload(orc.hot_gauge(L, 111))
+        assert lat.get_param("staple_form_active") == -1
         tab = lq.gradient_flow_measure(U, EPS, 6, 3)
         lq.flow_(U, lq.Gradientflow(U, Nflow=4, eps=EPS))
+        assert lat.get_param("staple_form_active") == 3      # the partitioned instance of the flow stage
         o = lq.gauge_flow_observables(U)
         close = lambda a, b: abs(a - b) <= 1e-13 * max(1.0, abs(b))
         assert np.abs(U.download() - r["U"]).max() < 1e-13

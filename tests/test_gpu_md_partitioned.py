@@ -49,12 +49,15 @@ def test_gauge_force_rccl_self_partition(lq, orc):
         U = orc.hot_gauge(L, 603)
         P = orc.gaussian_momenta(L, 604)
         Ud, Pd, G = lq.Gaugefields(lat).upload(U), lq.Gaugefields(lat).upload(P), lq.Gaugefields(lat)
+        assert lat.get_param("staple_form_active") == -1
         lq.gauge_force_(G, Ud, beta)
+        assert lat.get_param("staple_form_active") == 3      # the partitioned instance of the sweep
         Gref = orc.gauge_force(U, L, beta)
         assert np.abs(G.download() - Gref).max() / np.abs(Gref).max() < 1e-13
         lq.P_update_(Ud, Pd, 0.3, beta)
         Pref = orc.momentum_add_ta(P.copy(), 0.3, Gref, L)
         assert np.abs(Pd.download() - Pref).max() / np.abs(Pref).max() < 1e-13
+        assert lat.get_param("staple_form_active") == 3
         # the per-direction interface of the unchanged callers on the partitioned lattice: eager calls, one fused kernel per direction (three
         # directions only: the deferred triples run one by one), and all four (one fused four-direction call) give the same momenta
         ga = lq.GaugeAction(Ud)
