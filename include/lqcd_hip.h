@@ -85,7 +85,10 @@ int lqcd_ctx_sync(lqcd_ctx_t ctx);
  * all bit-identical: 2 [default]: scalar (wave-uniform) addressing, one workgroup per chunk, 12-real fp64 links only; 1: persistent workgroups with the next chunk's
  * loads in flight across the barrier, per-XCD in-order queue -- pipe_per_cu / pipe_grid / pipe_min_chunks shape its grid; 3: pipe_chunks_per_wg consecutive chunks per
  * workgroup, pipelined; 0: plain variant 1.  Forms 1 and 3 measured slower, LABNOTES.md section 2 "Round 3"), mixed_pair32 (1 [default]: the mixed-precision Wilson
- * solvers use the fp32 site-pair kernel on unpartitioned lattices with T % 4 == 0; read-only pair32_active), mixed_links16 (that kernel reads its links as int16 fixed point;
+ * solvers use the fp32 site-pair kernel on unpartitioned lattices with T % 4 == 0; read-only pair32_active; read-only f32_form_active: the kernel form of the last
+ * fp32 stencil launch -- -1 none yet, 0 site-per-lane interior kernel, 1 direction-split, 2 its persistent form (dslash_pipe 1 / 3), 3 site pairs, 4 folded twin on a
+ * partitioned lattice, + 8 when an exterior launch followed; read-only mixed_fp64_iters / mixed_handoffs: fp64 iterations of, and number of, the hand-offs to the fp64
+ * solver in the last mixed-precision CG / even-odd BiCGStab / multi-shift solve -- 0 / 0 when the fp32 corrections reached eps), mixed_links16 (that kernel reads its links as int16 fixed point;
  * 1 [default]: in the even-odd BiCGStab of the action / force solves, 2: in every mixed-precision solver, 0: fp32 links), bicg_reliable (1: the fp32 chain of that BiCGStab goes on
  * behind a correction step instead of starting again; default 0), dw_fused_cg (1 [default]: Domainwall solves run the fused CG iteration on the five-dimensional launch), clover_hop_s (1 [default]: the hops of the even-odd Wilson-clover
  * solver run the scalar-addressing kernel with the inverse clover blocks in its epilogue), stag_both (1: the staggered split kernel issues the loads of both hops back to back);
@@ -573,6 +576,14 @@ int lqcd_bench_cg(lqcd_op_t op, lqcd_spinor_t x, lqcd_spinor_t b, int warm, int 
  * done != 0: the solver's done flag is raised for the launch (modes 1 and 2 then leave dst untouched).  norm2 = the sum of the |.|^2 partials of the launch */
 int lqcd_bench_stencil_epilogue(lqcd_op_t op, lqcd_spinor_t dst, lqcd_spinor_t src, lqcd_spinor_t in, int dagger, int mode, int tgauge, double coef, int done,
                                 double* norm2);
+
+/* the same for the fp32 operator of the mixed-precision solvers (fp32 build of the stencil / site-pair kernel, as lqcd_op_apply_f32 chooses it), fp64 caller fields:
+ * mode 0 dst = D in, sums[0] = sum of the launch's |dst|^2 partials; 1 (update mode of the inner CG) dst = src - coef D in with the same sum, done != 0: no-op, dst = src
+ * rounded to fp32; 2 one Schur application of the mixed even-odd BiCGStab on the even halves of FULL fields, dst_e = (1 - k^2 [A^-1] H_eo [A^-1] H_oe) in_e, with its
+ * epilogue sums[0..2] = Re, Im <z, dst> (conj != 0: <dst, z>), |dst|^2 and, if z2 is given (z = in only), sums[3..4] = Re, Im <z2, dst>; soa != 0: the [value][workgroup] layout of
+ * the partials.  sums: 5 doubles.  Mode 2 is refused where the fused even-odd chain does not run.  No Julia binding (test aid) */
+int lqcd_bench_stencil_f32(lqcd_op_t op, lqcd_spinor_t dst, lqcd_spinor_t src, lqcd_spinor_t in, lqcd_spinor_t z, lqcd_spinor_t z2, int dagger, int mode, double coef,
+                           int done, int conj, int soa, double* sums);
 
 /* CG session for externally timed windows (bench.py brackets these with its own barriers/clock):
  * begin = r = b - D^+D x, p = r; iterate = enqueue n iterations (exit test disabled) and wait; end = release scratch */

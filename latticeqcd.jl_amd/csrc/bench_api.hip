@@ -215,6 +215,21 @@ extern "C" int lqcd_bench_stencil_epilogue(lqcd_op_t op, lqcd_spinor_t dst, lqcd
     return st;
 }
 
+// the same for the fp32 build and the site-pair kernel: one launch of the stencil a mixed-precision solve on `op` would run (links, layout and kernel from mix_prepare),
+// with the epilogues of inner_cg32 (modes 0, 1) or one schur32 application of the mixed even-odd BiCGStab (mode 2, even halves of FULL fields) -- mixed.hip
+extern "C" int lqcd_bench_stencil_f32(lqcd_op_t op, lqcd_spinor_t dst, lqcd_spinor_t src, lqcd_spinor_t in, lqcd_spinor_t z, lqcd_spinor_t z2, int dagger, int mode,
+                                      double coef, int done, int conj, int soa, double* sums) {
+    LQCHK(check_full(op, dst, in, "lqcd_bench_stencil_f32"));
+    ARGCHK(mode >= 0 && mode <= 2 && sums && (mode != 1 || src) && (mode != 2 || z), "lqcd_bench_stencil_f32: bad arguments");
+    if (mode == 1) LQCHK(check_full(op, src, in, "lqcd_bench_stencil_f32"));
+    if (mode == 2) LQCHK(check_full(op, z, dst, "lqcd_bench_stencil_f32"));
+    if (mode == 2 && z2) LQCHK(check_full(op, z2, in, "lqcd_bench_stencil_f32"));
+    ARGCHK(mode != 2 || !z2 || z == in, "lqcd_bench_stencil_f32: the second inner product exists for z = in only (the <s, t>, |t|^2, <r0, t> launch of the merged chain)");
+    ARGCHK(in != dst, "lqcd_bench_stencil_f32: the hop operand must not be written");
+    HIPCHK(hipSetDevice(op->ctx->device));
+    return mixed_bench_stencil_f32(op, dst, src, in, z, z2, dagger, mode, coef, done, conj, soa, sums);
+}
+
 // CG session (externally timed windows); the state lives in the context, one open session per context
 namespace lqcd {
 struct CgSession { lqcd_op_s* op = nullptr; lqcd_spinor_s* x = nullptr; CgWork w; };

@@ -331,6 +331,9 @@ static int* param_ptr(lqcd_ctx_s* c, const char* key) {
     if (!strcmp(key, "mixed_xfuse")) return &c->tun.mixed_xfuse;
     if (!strcmp(key, "mixed_defer_x")) return &c->tun.mixed_defer_x;
     if (!strcmp(key, "pair32_active")) return &c->tun.pair32_active;
+    if (!strcmp(key, "f32_form_active")) return &c->tun.f32_form_active;
+    if (!strcmp(key, "mixed_fp64_iters")) return &c->tun.mixed_fp64_iters;
+    if (!strcmp(key, "mixed_handoffs")) return &c->tun.mixed_handoffs;
     if (!strcmp(key, "stag_both")) return &c->tun.stag_both;
     if (!strcmp(key, "clover_fused")) return &c->tun.clover_fused;
     if (!strcmp(key, "clover_transport")) return &c->tun.clover_transport;

@@ -705,6 +705,11 @@ struct Tunables {
                                   // eps = 1e-16 and a solve takes 11.4 instead of 13.0 ms at 32^3 x 64; 2: in every mixed-precision solver (the CG on D^+D loses: 49.5 vs
                                   // 46.5 ms, a fourth restart); 0: fp32 links
     int pair32_active = 0;    // read-only: the last mixed-precision solve / lqcd_op_apply_f32 ran the fp32 site-pair kernel
+    int f32_form_active = -1; // read-only: the kernel form of the last launch of the fp32 build of the stencil (stencil.hip -DLQCD_F32, launch_pair32_interior); -1 no fp32 launch yet,
+                              // 0 site-per-lane interior kernel (wilson_interior / staggered_interior), 1 direction-split, 2 persistent direction-split (dslash_pipe 1 / 3), 3 site pairs
+                              // (stencil_pair32.hip), 4 folded twin of the direction-split kernel (partitioned lattice, no exterior launch); + 8: an exterior launch followed (interior + exterior)
+    int mixed_fp64_iters = 0; // read-only: fp64 iterations of the hand-off in the last mixed-precision CG / even-odd BiCGStab / multi-shift solve (0: the fp32 corrections reached eps)
+    int mixed_handoffs = 0;   // read-only: how many times that solve handed a system to the fp64 solver (a correction step that failed to gain its factor)
     int recon_active = 0;     // read-only: 1 if the last operator application used the 12-real links, 2: rows 0, 1 + the fp32 deviation of row 2 ("12 + delta")
     int bicg_mixed = 0;       // 1: the even-odd BiCGStab of the plain Wilson operator (lqcd_solve_bicgstab_eo, and through it the action / force solves) runs the fp32 chain
                               // inside an fp64 defect correction; the stopping rule holds for the true fp64 residual.  mixed_action_solver = 1 switches it on for the action solves

@@ -787,6 +787,7 @@ int bicgstab_eo_wilson_mixed(lqcd_op_s* op, lqcd_spinor_s& xe, lqcd_spinor_s* rh
                              int maxiter, int* iters, double* final_rr, const double2* Ai) {
     lqcd_ctx_s* c = op->ctx;
     const size_t nh = xe.elems, nfull = 2 * nh;
+    c->tun.mixed_fp64_iters = 0; c->tun.mixed_handoffs = 0;      // (read-only keys: the hand-off of THIS solve)
     // fp32 links and work space: the buffers of the mixed-precision CG (four full-lattice vectors = eight halves), component-pair layout
     Mix32 mm;
     LQCHK(mix_prepare(op, nfull, mm, true));       // layout 2 (site pairs) where stencil_pair32.hip applies, else the component pairs of the fp32 build
@@ -888,6 +889,7 @@ int bicgstab_eo_wilson_mixed(lqcd_op_s* op, lqcd_spinor_s& xe, lqcd_spinor_s* rh
     c->zero_guess_hint = false;      // (x is the current iterate now, whatever the caller said about its guess)
     const int st = bicgstab_eo_wilson(op, xe, rhs, w, to, dg, eps, std::max(1, maxiter - total), &it64, final_rr, Ai);
     c->zero_guess_hint = hint;
+    c->tun.mixed_handoffs = 1; c->tun.mixed_fp64_iters = it64;
     if (iters) *iters = total + it64;
     return st;
 }
@@ -955,6 +957,101 @@ static int inner_ms32(lqcd_op_s* op, const Mix32& m, float2* xbase, const std::v
     return LQCD_OK;
 }
 
+
+// One launch of the fp32 stencil with the epilogues the inner solvers steer by, on fp64 caller fields (tests: lqcd_bench_stencil_f32, bench_api.hip).  The links, the
+// layout, the kernel and the number of partials are the ones a mixed-precision solve on `op` would get from mix_prepare under the tunables in force.
+//   mode 0  dst = D in                      sums[0] = sum of the launch's |dst|^2 partials (the first launch of an inner_cg32 iteration)
+//   mode 1  dst = src - coef D in           sums[0] = sum of the |dst|^2 partials (its update-mode second launch; done: the launch is a no-op, dst = src rounded to fp32)
+//   mode 2  dst_e = (1 - k^2 [A^-1] H_eo [A^-1] H_oe) in_e on the even halves of FULL fields (one schur32 application), sums[0..2] = <z, dst> (conj: <dst, z>), |dst|^2,
+//           sums[3..4] = <z2, dst> if z2 is given (only with z = in, as the kernels have it); soa: the [value][workgroup] layout of the partials.  Only where the fused even-odd chain runs (lqcd_solve_bicgstab_eo).
+int mixed_bench_stencil_f32(lqcd_op_s* op, lqcd_spinor_s* dst, lqcd_spinor_s* src, lqcd_spinor_s* in, lqcd_spinor_s* z, lqcd_spinor_s* z2, int dagger, int mode,
+                            double coef, int done, int conj, int soa, double* sums) {
+    lqcd_ctx_s* c = op->ctx;
+    const size_t n = in->elems, nh = n / 2;
+    const bool clov = op->csw != 0.0 && op->clover != nullptr;
+    VariantPin pin(c);
+    Mix32 m;
+    for (int k = 0; k < 5; k++) sums[k] = 0.0;
+    if (mode < 2) {
+        LQCHK(mix_prepare(op, n, m));
+        const int nbs = stencil_num_partials(c, op->kind, op->r, 2, m.layout == 2 ? 2 : 1, clov);
+        double sc[3] = {coef, coef, (mode == 1 && done) ? 1.0 : 0.0};      // S_ALPHA, S_BETA, S_DONE
+        static_assert(S_BETA == S_ALPHA + 1 && S_DONE == S_ALPHA + 2, "mixed_bench_stencil_f32: scalar slots");
+        HIPCHK(hipMemcpyAsync(c->d_scal + S_ALPHA, sc, sizeof(sc), hipMemcpyHostToDevice, c->stream));
+        apply_bc(c, op->bc);
+        int st;
+        if (mode == 0) {
+            LQCHK(to_f32(c, m.layout, m.p, in->data, n, 1.0));
+            StencilCall s1 = call32(op, m, m.t, m.p, dagger);
+            s1.norm_partial = c->d_partial;
+            s1.skip_flag = c->d_scal;
+            st = stencil_apply(c, s1);
+        } else {
+            LQCHK(to_f32(c, m.layout, m.r, src->data, n, 1.0));
+            LQCHK(to_f32(c, m.layout, m.t, in->data, n, 1.0));
+            StencilCall s2 = call32(op, m, m.t, m.t, dagger);      // update mode: nothing is written to out
+            s2.norm_partial = c->d_partial;
+            s2.upd_scal = c->d_scal;
+            s2.upd[0] = (double2*)m.r;
+            s2.upd[1] = (double2*)(m.r + m.blk);
+            st = stencil_apply(c, s2);
+        }
+        if (st == LQCD_OK) st = reduce_to_slot(c, nbs, 1, S_PQ, true);
+        sc[2] = 0.0;
+        HIPCHK(hipMemcpyAsync(c->d_scal + S_ALPHA, sc, sizeof(sc), hipMemcpyHostToDevice, c->stream));
+        LQCHK(st);
+        HIPCHK(hipMemsetAsync(dst->data, 0, n * sizeof(double2), c->stream));
+        LQCHK(add_from_f32(c, m.layout, dst->data, mode == 0 ? m.t : m.r, 1.0, n));
+        HIPCHK(hipMemcpyAsync(c->h_scal, c->d_scal + S_PQ, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        sums[0] = c->h_scal[0];
+        return LQCD_OK;
+    }
+    // mode 2: the conditions of the fused chain (bicgstab_eo.hip lqcd_solve_bicgstab_eo)
+    if (!(op->kind == LQCD_WILSON && c->tun.bicg_fused >= 1 && op->r == 1.0 && c->tun.dslash_variant == 1 && !any_partitioned(c) && !c->has_comm && c->geom.Vh % 64 == 0)) {
+        set_error("lqcd_bench_stencil_f32: mode 2 needs what the fused even-odd BiCGStab needs (Wilson r = 1, dslash_variant = 1, one unpartitioned GPU, whole chunks per parity)");
+        return LQCD_ERR_UNSUPPORTED;
+    }
+    LQCHK(mix_prepare(op, n, m, true));
+    Eo32 e;
+    e.layout = m.layout;
+    e.gauge = m.gauge; e.gauge12 = m.gauge12; e.gauge16 = m.gauge16;
+    if (clov) {      // A^-1 follows A (which mix_prepare has brought up to the links), in fp32 in the slot of the fp32 clover blocks (bicgstab_eo_wilson_mixed)
+        if (!op->clover_inv) HIPCHK(hipMalloc((void**)&op->clover_inv, clover_elems(c->geom) * sizeof(double2)));
+        if (op->clover_inv_version != op->clover_version) {
+            LQCHK(clover_invert(c, op->clover, op->clover_inv));
+            op->clover_inv_version = op->clover_version;
+        }
+        const size_t nc = clover_elems(c->geom);
+        LQCHK(mix_alloc(c, 6, nc * sizeof(float2)));
+        hipLaunchKernelGGL(cvt_to_f32, dim3(stream_grid(c, nc)), dim3(MB), 0, c->stream, (float2*)c->mix_buf[6], op->clover_inv, nc, 1.0);
+        HIPCHK(hipGetLastError());
+        e.ainv = (const float2*)c->mix_buf[6];
+    }
+    e.x = m.x; e.r = m.x + nh; e.r0 = m.r; e.p = m.r + nh; e.v = m.p; e.s = m.p + nh; e.t = m.t; e.to = m.t + nh;
+    auto half_to_f32 = [&](float2* d, lqcd_spinor_s* f) -> int {
+        if (e.layout == 2) return pair32_cvt_spinor(c, d, f->data, 1.0, 1);
+        return to_f32(c, 1, d, f->data, nh, 1.0);
+    };
+    LQCHK(half_to_f32(e.p, in));
+    const float2* z32 = e.p;      // z = in: the form of the chain's second Schur application (<s, t>), the only one with a second inner product (the kernels keep z2 in z's registers)
+    if (z != in) { LQCHK(half_to_f32(e.r0, z)); z32 = e.r0; }
+    if (z2) LQCHK(half_to_f32(e.s, z2));
+    const double zero = 0.0;
+    HIPCHK(hipMemcpyAsync(c->d_scal + B_DONE, &zero, sizeof(double), hipMemcpyHostToDevice, c->stream));
+    apply_bc(c, op->bc);
+    const int nbs = e.layout == 2 ? pair32_num_blocks(c) / 2 : (c->geom.Vh + 63) / 64, nv = z2 ? 5 : 3;
+    LQCHK(schur32(op, e, e.v, e.p, z32, c->d_partial, conj ? 1 : 0, dagger ? 1 : 0, c->d_scal + (B_DONE - S_DONE), z2 ? e.s : nullptr, soa != 0));
+    LQCHK(reduce_to_slot(c, nbs, nv, B_TS5, true, 0, c->d_partial, soa != 0));
+    HIPCHK(hipMemsetAsync(dst->data, 0, n * sizeof(double2), c->stream));
+    if (e.layout == 2) LQCHK(pair32_axpy_to_f64(c, dst->data, e.v, 1.0, 1));
+    else LQCHK(add_from_f32(c, 1, dst->data, e.v, 1.0, nh));
+    HIPCHK(hipMemcpyAsync(c->h_scal, c->d_scal + B_TS5, 5 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < nv; k++) sums[k] = c->h_scal[k];
+    return LQCD_OK;
+}
+
 }  // namespace lqcd
 
 using namespace lqcd;
@@ -1004,6 +1101,7 @@ extern "C" int lqcd_solve_mixed_cg_DdagD(lqcd_op_t op, lqcd_spinor_t x, lqcd_spi
            "lqcd_solve_mixed_cg_DdagD: need two distinct FULL spinors of the operator's kind on the operator's context");
     lqcd_ctx_s* c = op->ctx;
     HIPCHK(hipSetDevice(c->device));
+    c->tun.mixed_fp64_iters = 0; c->tun.mixed_handoffs = 0;      // (read-only keys: the hand-off of THIS solve)
     const bool adaptive = inner_tol <= 0.0;       // default: the fewest defect-correction steps fp32 allows, the required reduction split evenly over them
     const size_t n = x->elems;
     VariantPin pin(c);
@@ -1070,6 +1168,7 @@ extern "C" int lqcd_solve_mixed_cg_DdagD(lqcd_op_t op, lqcd_spinor_t x, lqcd_spi
             int it64 = 0;
             const int s64 = cg_run(op, x, b, eps, maxiter - total, false, &it64, nullptr);
             total += it64;
+            c->tun.mixed_handoffs = 1; c->tun.mixed_fp64_iters = it64;
             if (s64 != LQCD_OK && s64 != LQCD_ERR_NOT_CONVERGED) return s64;
             LQCHK(true_residual());
         }
@@ -1116,6 +1215,7 @@ extern "C" int lqcd_solve_multishift_mixed_cg(lqcd_op_t op, lqcd_spinor_t x0, lq
     if (x0) LQCHK(check_full(op, x0, b, "lqcd_solve_multishift_mixed_cg"));
     lqcd_ctx_s* c = op->ctx;
     HIPCHK(hipSetDevice(c->device));
+    c->tun.mixed_fp64_iters = 0; c->tun.mixed_handoffs = 0;      // (read-only keys: the hand-offs of THIS solve, summed over its systems)
     if (inner_tol <= 0.0) inner_tol = 1e-6;     // about as far as an fp32 recurrence follows the true residual
     const size_t n = b->elems, bytes64 = n * sizeof(double2);
     VariantPin pin(c);
@@ -1197,6 +1297,7 @@ extern "C" int lqcd_solve_multishift_mixed_cg(lqcd_op_t op, lqcd_spinor_t x0, lq
                 const int s64 = j < 0 ? lqcd_solve_multishift_cg(op, e64, nullptr, rhs, nullptr, 0, eps, maxiter - total, &it64, &r64)
                                       : lqcd_solve_multishift_cg(op, nullptr, ex, rhs, &sg, 1, eps, maxiter - total, &it64, &r64);
                 total += it64;
+                c->tun.mixed_handoffs += 1; c->tun.mixed_fp64_iters += it64;
                 if (s64 != LQCD_OK && s64 != LQCD_ERR_NOT_CONVERGED) return s64;
                 LQCHK(blas_axpy(c, 1.0, 0.0, e64->data, x->data, n));
                 LQCHK(true_residual(x, sg));

@@ -147,6 +147,9 @@ int bicgstab_eo_wilson(lqcd_op_s* op, lqcd_spinor_s& xe, lqcd_spinor_s* rhs, lqc
 // mixed.hip: the same solve with an fp32 inner chain and fp64 defect correction (plain Wilson, 12-real links); outer: correction steps
 int bicgstab_eo_wilson_mixed(lqcd_op_s* op, lqcd_spinor_s& xe, lqcd_spinor_s* rhs, lqcd_spinor_s* const w[6], lqcd_spinor_s* to, int dg, double eps,
                              int maxiter, int* iters, double* final_rr, const double2* Ai = nullptr);
+// mixed.hip: one launch of the fp32 stencil with the inner solvers' epilogues on fp64 caller fields (lqcd_bench_stencil_f32)
+int mixed_bench_stencil_f32(lqcd_op_s* op, lqcd_spinor_s* dst, lqcd_spinor_s* src, lqcd_spinor_s* in, lqcd_spinor_s* z, lqcd_spinor_s* z2, int dagger, int mode,
+                            double coef, int done, int conj, int soa, double* sums);
 
 // stencil_mrhs.hip: the direction-split parity hop on several columns that share the links, out_j = a xin_j + b H in_j (Wilson r = 1, fp64, one unpartitioned GPU)
 struct MrhsCall {

@@ -2172,10 +2172,11 @@ int launch_stencil_interior(lqcd_ctx_s* c, const StencilCall& s) {
         const bool delta = s.gauge12_delta && !kF32Build && s.kind == LQCD_WILSON && k.gauge12 && !k.alpha_partials && !k.dot_partial && !s.clover_on_hop && !k.clover && !s.fold &&
                            c->tun.dslash_pipe == 2 && wilson_pipe_applies(c, s.kind, s.r, s.parity_mode, false);
         if (s.gauge12_delta && !delta) { k.gauge12 = nullptr; c->tun.recon_active = 0; }
+        int form32 = 1;      // read-only key f32_form_active (fp32 build): 1 direction-split, 2 its persistent form, 4 its folded twin
         if (s.fold) {      // folded halo schedule: the scalar-addressing FOLD instances where they exist, the folded twins of the direction-split kernels otherwise
             const bool sdir = !kF32Build && s.kind == LQCD_WILSON && s.r == 1.0 && !k.clover && !s.clover_on_hop && !k.dot_partial && !k.alpha_partials && s.dw_ls <= 1 &&
                               !k.g.part[0] && c->tun.dslash_pipe == 2 && (k.gauge12 || c->tun.dslash_s18) && wilson_pipe_applies(c, s.kind, s.r, s.parity_mode, false);
-            if (!sdir) return launch_dirsplit_fold(c, s, k);
+            if (!sdir) { if (kF32Build) c->tun.f32_form_active = 4; return launch_dirsplit_fold(c, s, k); }
         }
         if (s.kind == LQCD_STAGGERED) {
             const bool both = c->tun.stag_both && !(c->geom.part[0] || c->geom.part[1] || c->geom.part[2] || c->geom.part[3]);
@@ -2255,6 +2256,7 @@ int launch_stencil_interior(lqcd_ctx_s* c, const StencilCall& s) {
                                                                                   // round 4 also for the 18 stored reals (no spill once the diagonal term / old r load behind the hops)
             PipeArgs a = make_pipe_args(c, k, s);
             const bool persist = c->tun.dslash_pipe == 1 || c->tun.dslash_pipe == 3;
+            if (persist) form32 = 2;
             if (c->tun.dslash_pipe == 3) { a.ctr = nullptr; a.per_wg = wilson_pipe_per_wg(c, k.nblocks); }
             const dim3 pg(c->tun.dslash_pipe == 1 ? wilson_pipe_grid(c, k.nblocks, s.prec) : c->tun.dslash_pipe == 3 ? k.nblocks / a.per_wg : k.nblocks), pb(256);
             const bool ntb = (k.nt & 1) != 0;
@@ -2333,8 +2335,10 @@ int launch_stencil_interior(lqcd_ctx_s* c, const StencilCall& s) {
             }
         }
         HIPCHK(hipGetLastError());
+        if (kF32Build) c->tun.f32_form_active = form32;
         return LQCD_OK;
     }
+    if (kF32Build) c->tun.f32_form_active = 0;      // the site-per-lane kernels (wilson_interior, staggered_interior)
     switch (c->tun.dslash_block) {
     case 64: return launch_interior_tb<64>(c, s);
     case 256: return launch_interior_tb<256>(c, s);
@@ -2411,6 +2415,7 @@ int launch_stencil_exterior(lqcd_ctx_s* c, const StencilCall& s) {
     const int nt = max_face_threads(c, s.parity_mode);
     if (nt == 0) return LQCD_OK;
     HArgs h = make_hargs(c, s);
+    if (kF32Build && c->tun.f32_form_active >= 0) c->tun.f32_form_active |= 8;      // interior + exterior (the interior launch is always issued first)
     if (s.kind != LQCD_WILSON) h.pack_next = -1;      // only the Wilson exterior packs for a following application
     if (h.pack_next >= 0) c->halo_epoch++;
     dim3 grid((nt + 127) / 128, 8), block(128);

@@ -566,6 +566,7 @@ int launch_pair32_interior(lqcd_ctx_s* c, const StencilCall& s) {
     ARGCHK(s.kind == LQCD_WILSON && s.r == 1.0 && s.gauge12 && !s.clover && !s.alpha_partials && pair32_geometry_ok(c),
            "pair32 stencil: Wilson r = 1 with 12-real links on an unpartitioned lattice only");
     ARGCHK(!(s.dot_partial && s.upd_scal), "pair32 stencil: dot mode and update mode exclude each other");
+    c->tun.f32_form_active = 3;      // (read-only key: the site-pair kernel)
     const Geom& g = c->geom;
     PairArgs a;
     a.gauge = (const float4*)s.gauge12;

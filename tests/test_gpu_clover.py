@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_err
+from f32_bound import no_handoff, planned_steps
 
 pytestmark = pytest.mark.gpu
 
@@ -51,6 +52,9 @@ def test_wilson_clover_matches_oracle(lq, orc, L):
     itm, outer, rrm = lq.solve_mixed_DinvX_(sol, lq.DdagD_operator(D), x, return_info=True)
     xo2, _, _, st2 = orc.cg_clover(Uh2, A2, psi, L, KAPPA, 1.0, BC, eps=1e-19)
     assert st2 == 0 and rrm < 1e-19 and outer >= 2 and rel_err(sol.download(), xo2) < 1e-8
+    no_handoff(lat, "mixed CG, clover %s" % (L,))
+    steps = planned_steps(1e-19, float(np.vdot(psi, psi).real))
+    assert steps <= outer <= steps + 1 and lat.get_param("f32_form_active") == 1, (outer, steps)
     lq.mul_(y, lq.DdagD_operator(D), sol)
     lq.add_fermion_(y, -1.0, x)
     assert lq.dot(y, y).real < 1e-19
@@ -147,6 +151,7 @@ def test_rccl_self_partition_clover(lq, orc):
         lq.clear_fermion_(sol)
         lq.solve_mixed_DinvX_(sol, lq.DdagD_operator(D), x)
         assert rel(sol.download(), xo) < 1e-8
+        assert lat.get_param("mixed_handoffs") == 0 and lat.get_param("mixed_fp64_iters") == 0, "the mixed CG handed off to the fp64 CG"
         D.method_CG = "bicgstab_evenodd"
         lq.clear_fermion_(sol)
         lq.solve_DinvX_(sol, D, x)

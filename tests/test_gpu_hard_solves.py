@@ -42,6 +42,7 @@ import numpy as np
 import pytest
 
 import hard_systems as hs
+from f32_bound import no_handoff
 
 pytestmark = pytest.mark.gpu
 
@@ -230,6 +231,7 @@ def test_multishift(lq, orc, mixed):
     if mixed:
         it, outer, rr = lq.shiftedcg_mixed(xs, list(s["sigmas"]), x, A, b, return_info=True)
         print("shiftedcg_mixed: %d fp32 iterations, %d correction solves, largest true rr %.4e, %.3f s" % (it, outer, rr, time.perf_counter() - t0))
+        no_handoff(lat, "shiftedcg_mixed")      # ill-conditioned, eps = 1e-16: more correction solves, none of them handed to the fp64 solver
     else:
         it, rr = lq.shiftedcg(xs, list(s["sigmas"]), x, A, b, return_info=True)
         print("shiftedcg: %d iterations in %.3f s" % (it, time.perf_counter() - t0))
@@ -251,6 +253,7 @@ def test_mixed_cg(lq, orc, pair32):
     it, outer, rr = lq.solve_mixed_DinvX_(x, lq.DdagD_operator(D), b, return_info=True)
     print("mixed cg pair32 %d: %d inner iterations, %d outer corrections, reported true rr %.4e, %.3f s" % (pair32, it, outer, rr, time.perf_counter() - t0))
     assert lat.get_param("pair32_active") == pair32
+    no_handoff(lat, "mixed cg pair32 %d" % pair32)
     hold(orc, s, x.download(), rr, "mixed cg pair32 %d" % pair32)
 
 
@@ -292,6 +295,7 @@ def test_evenodd_bicgstab_mixed_chain(lq, orc, links16, reliable, row):
     s, lat, U, D, b = wilson(lq, orc, row, (("bicg_mixed", 1), ("mixed_links16", links16), ("bicg_reliable", reliable)), method="bicgstab_evenodd")
     xh, it, rr = eo_solve(lq, s, D, b)
     assert lat.get_param("pair32_active") == 1
+    no_handoff(lat, "bicgstab_eo mixed links16 %d reliable %d" % (links16, reliable))
     hold(orc, s, xh, rr, "bicgstab_eo mixed links16 %d reliable %d" % (links16, reliable), dagger=s["dagger"])
 
 
@@ -379,6 +383,13 @@ def action_and_force(lq, orc, mixed, eo):
           % (mixed, eo, it, S, Sref, dS, ACTION_BOUND, dG, FORCE_BOUND, dt))
     assert lat.get_param("mixed_action_solver") == mixed and lat.get_param("action_eo_solver") == eo
     assert lat.get_param("pair32_active") == mixed              # a fresh context: an fp32 operator was set up if and only if a mixed solver ran
+    if mixed and not eo:
+        no_handoff(lat, "action through the mixed CG")      # (the solve of the force evaluation, the last one)
+    elif mixed:
+        # by design: at this kappa the fp32 chain of the first even-odd solve stalls, bicgstab_eo_wilson_mixed hands the Schur system to the fp64 chain -- once per
+        # solve -- which stalls as well; the second even-odd solve is then not tried and the fp64 CG on the normal equations (no mixed solver) finishes
+        print("action eo mixed: mixed_handoffs %d mixed_fp64_iters %d" % (lat.get_param("mixed_handoffs"), lat.get_param("mixed_fp64_iters")))
+        assert lat.get_param("mixed_handoffs") == 1 and lat.get_param("mixed_fp64_iters") > 0
     fa.close()
     return s, it, S, Sref, dS, dG, Xh, Yh, Gh
 

@@ -3,6 +3,7 @@ mixed_action_solver): the stopping rule is enforced on the true fp64 residual, s
 import numpy as np
 import pytest
 
+from f32_bound import no_handoff
 from test_gpu_md import BETA, KAPPA, REF_PLAQ_WILSON_HMC, DeviceHMC, _fixture
 
 pytestmark = pytest.mark.gpu
@@ -19,6 +20,7 @@ def test_hmc_with_mixed_precision_action_solver(lq, orc):
     print("mixed-solver HMC: dH =", ["%.3f" % d for d in h.dH], "accepted", sum(h.accepted), "/ 10, plaquette", plaq)
     assert abs(plaq - REF_PLAQ_WILSON_HMC) / REF_PLAQ_WILSON_HMC < 0.1
     assert sum(h.accepted) >= 6 and np.abs(np.array(h.dH)).max() < 2.0
+    no_handoff(U.lattice, "last pseudofermion solve of the HMC stream")
     # same seeds, same integrator: the fp64-solver run of test_gpu_md.py gives dH within solver tolerance of these
     U2 = _fixture(lq)[2]
     h2 = DeviceHMC(lq, U2, KAPPA, BETA, dtau=0.05, mdsteps=20, nsw=10, seed=111)

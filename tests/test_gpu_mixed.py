@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_err
+from f32_bound import no_handoff, planned_steps
 
 pytestmark = pytest.mark.gpu
 
@@ -45,6 +46,9 @@ def test_mixed_cg_matches_oracle_fp64_solution(gpu, orc, kind_name, L, bc):
     A = lq.DdagD_operator(D)
     it, outer, rr = lq.solve_mixed_DinvX_(x, A, b, return_info=True)
     assert rr < 1e-19 and outer >= 2          # more than one correction step is needed to get from fp32 to 1e-19
+    no_handoff(lat, "mixed CG %s %s" % (kind_name, L))
+    steps = planned_steps(1e-19, float(np.vdot(b_h, b_h).real))
+    assert steps <= outer <= steps + 1, (outer, steps)      # the solver's own plan, one more step allowed
     xo, ito, rro, st = orc.cg_DdagD(okind, Uh, b_h, L, km, 1.0, bc, eps=1e-19)
     assert st == 0 and rel_err(x.download(), xo) < 1e-9
     assert it < 3 * ito + 20                  # restarts cost iterations, but not many
@@ -72,6 +76,11 @@ def test_mixed_cg_tight_and_loose_targets(gpu, orc):
         lq.mul_(r, A, x)
         lq.add_fermion_(r, -1.0, b)
         assert lq.dot(r, r).real < eps and rr < eps
+        # also at 1e-24, 29 orders below |b|^2 ~ 1e5: the floor rounding puts under the fp64 residual of this system (u64 |A| |x| ~ 1e-14 in norm) lies below it,
+        # so every planned step gains its factor and nothing is handed to the fp64 CG
+        no_handoff(lat, "mixed CG eps %g" % eps)
+        steps = planned_steps(eps, lq.dot(b, b).real)
+        assert outer <= steps + 1, (eps, outer, steps)
     # non-convergence raises like the fp64 solver
     D.MaxCGstep = 3
     A = lq.DdagD_operator(D)
@@ -99,6 +108,8 @@ def test_mixed_cg_under_every_stencil_variant_setting(gpu, orc, variant):
         assert lat.get_param("dslash_variant") == variant
         xo, ito, rro, st = orc.cg_DdagD(orc.WILSON, Uh, b_h, L, KAPPA, 1.0, BC, eps=1e-19)
         assert st == 0 and rr < 1e-19 and rel_err(x.download(), xo) < 1e-9
+        no_handoff(lat, "dslash_variant %d" % variant)
+        assert lat.get_param("f32_form_active") == (0 if variant == 0 else 1)      # site-per-lane / direction-split (8.8.4.8 does not take the pair kernel)
     finally:
         lat.set_param("dslash_variant", 1)
 
@@ -125,6 +136,7 @@ def test_mixed_multishift_matches_oracle_and_true_residuals(gpu, orc, kind_name,
     A = lq.DdagD_operator(D)
     it, outer, worst = lq.shiftedcg_mixed(xs, sig, x0, A, b, eps=1e-20, return_info=True)
     assert worst < 1e-20 and outer >= len(sig)           # fp32 cannot reach 1e-20: every system needs at least one correction
+    no_handoff(lat, "mixed multi-shift eps 1e-20")      # every system reaches 1e-20 by fp32 corrections: none is redone in fp64
     o0, oxs, oit, oresid, st = orc.multishift_cg(okind, Uh, b_h, L, km, sig, eps=1e-20)
     assert st == 0
     if with_base:
@@ -170,6 +182,7 @@ def test_mixed_multishift_rhmc_poles_and_zeta_underflow(gpu, orc):
     it, outer, worst = lq.shiftedcg_mixed(xs, sig, None, A, b, eps=1e-18, return_info=True)
     _, oxs, oit, _, st = orc.multishift_cg(orc.STAGGERED, Uh, b_h, L, m, sig, bc=BC, eps=1e-18)
     assert st == 0 and worst < 1e-18
+    no_handoff(lat, "mixed multi-shift, RHMC poles")
     for x, ox in zip(xs, oxs):
         xh = x.download()
         assert np.isfinite(xh).all() and rel_err(xh, ox) < 1e-8
@@ -195,6 +208,7 @@ def test_mixed_cg_rccl_self_partition(gpu, orc):
             it, outer, rr = lq.solve_mixed_DinvX_(x, lq.DdagD_operator(D), b, return_info=True)
             xo, ito, rro, st = orc.cg_DdagD(kind, U, psi, L, km, 1.0, BC, eps=1e-19)
             assert st == 0 and rr < 1e-19 and np.abs(x.download() - xo).max() / np.abs(xo).max() < 1e-9, (name, it, outer, rr)
+            assert lat.get_param("mixed_handoffs") == 0 and lat.get_param("mixed_fp64_iters") == 0, (name, "handed off to the fp64 CG")
         print("MIXED_SELF_OK")
     """)
     for mask in ("8", "14"):
@@ -229,6 +243,8 @@ def test_mixed_cg_full_size_is_faster_than_fp64(gpu):
     print("fp64 %.1f ms %s true rr %.2e | mixed %.1f ms %s true rr %.2e" % (1e3 * res["fp64"][0], res["fp64"][1], res["fp64"][2],
                                                                            1e3 * res["mixed"][0], res["mixed"][1], res["mixed"][2]))
     assert res["mixed"][2] < 1e-16 and res["fp64"][2] < 2e-16
+    no_handoff(lat, "mixed CG 32^3x64")      # (the keys are written by the mixed solve alone: the last call of the loop)
+    assert lat.get_param("f32_form_active") == 3 and res["mixed"][1][1] <= planned_steps(1e-16, lq.dot(b, b).real) + 1
     assert res["mixed"][0] < res["fp64"][0]
     for o in (x, b, D, U):
         o.close()
@@ -252,6 +268,9 @@ def test_mixed_cg_on_non_unitary_links_uses_the_18_real_inner_operator(gpu, orc)
     assert st == 0 and rr < 1e-18 and rel_err(x.download(), xo) < 1e-8
     assert lat.get_param("recon_active") == 0
     assert outer >= 2 and it < 3 * ito + 20          # defect correction converges in fp32 steps: no stall, no fp64 fall-back
+    no_handoff(lat, "non-unitary links")
+    steps = planned_steps(1e-18, float(np.vdot(b_h, b_h).real))
+    assert steps <= outer <= steps + 1, (outer, steps)
 
 
 @pytest.mark.parametrize("kind_name,L", [("Wilson", (16, 8, 8, 4)), ("Wilson", (4, 4, 4, 8)), ("Staggered", (8, 4, 6, 4)), ("WilsonClover", (4, 4, 4, 8))])
@@ -276,6 +295,7 @@ def test_deferred_x_update_of_the_fp32_solver_gives_identical_results(gpu, orc, 
         x = b.similar()
         try:
             info = lq.solve_mixed_DinvX_(x, A, b, return_info=True)
+            no_handoff(lat, "mixed_defer_x %d %s %s" % (defer, kind_name, L))
         except lq.NotConverged:
             info = None
         out.append((info, x.download()))
@@ -308,6 +328,7 @@ def test_mixed_precision_evenodd_bicgstab_wilson_clover(gpu, orc):
         it32, rr32 = lq.solve_DinvX_(x32, Dd, b, return_info=True)
         lat.set_param("bicg_mixed", 0)
         assert rr32 < 1e-19 and rel_err(x32.download(), x64.download()) < 1e-9
+        no_handoff(lat, "mixed even-odd BiCGStab, clover, dagger %d" % dagger)
         res = b.download() - orc.wilson_clover_D(Uh, A, x32.download(), L, KAPPA, 1.0, (1, 1, 1, -1), dagger=dagger)
         assert np.vdot(res, res).real < 1e-19
     fa = lq.FermiAction(D)
@@ -318,6 +339,7 @@ def test_mixed_precision_evenodd_bicgstab_wilson_clover(gpu, orc):
     lat.set_param("mixed_action_solver", 1)
     S1 = lq.calc_UdSfdU_(G1, fa, U, eta)
     lat.set_param("mixed_action_solver", 0)
+    no_handoff(lat, "clover action through the mixed even-odd BiCGStab")      # (the last of its two Schur solves)
     assert abs(S1 - S0) < 1e-10 * abs(S0) and rel_err(G1.download(), G0.download()) < 1e-8
 
 
@@ -350,6 +372,7 @@ def test_mixed_precision_evenodd_bicgstab_keeps_the_stopping_rule(gpu, orc, L, d
     lat.set_param("bicg_reliable", 0)
     assert lat.get_param("pair32_active") == (1 if L[0] == 16 else 0)
     assert rr32 < 1e-19 and it32 >= it64           # the fp32 iterations of all correction steps together
+    no_handoff(lat, "mixed even-odd BiCGStab links16 %d reliable %d" % (links16, reliable))
     assert rel_err(x32.download(), x64.download()) < 1e-9
     orc.set_threads(os.cpu_count() or 1)
     try:
@@ -366,8 +389,10 @@ def test_mixed_precision_evenodd_bicgstab_keeps_the_stopping_rule(gpu, orc, L, d
     lq.calc_UdSfdU_(G0, fa, U, eta)
     lat.set_param("mixed_action_solver", 1)
     S1 = lq.evaluate_FermiAction(fa, U, eta)
+    no_handoff(lat, "Wilson action through the mixed even-odd BiCGStab")
     lq.calc_UdSfdU_(G1, fa, U, eta)
     lat.set_param("mixed_action_solver", 0)
+    no_handoff(lat, "Wilson force through the mixed even-odd BiCGStab")
     assert abs(S1 - S0) < 1e-10 * abs(S0) and rel_err(G1.download(), G0.download()) < 1e-8
 
 
@@ -418,6 +443,7 @@ def test_mixed_evenodd_chain_merged_update_and_its_guard(gpu, orc):
         x = b.similar()
         it, rr = lq.solve_DinvX_(x, D, b, return_info=True)
         assert rr < 1e-19 and lat.get_param("pair32_active") == 1, (fused, guard)
+        no_handoff(lat, "bicg_fused %d guard %d" % (fused, guard))
         r = b.similar()
         lq.mul_(r, D, x)
         lq.add_fermion_(r, -1.0, b)

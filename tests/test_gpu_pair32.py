@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_err
+from f32_bound import no_handoff, planned_steps
 
 pytestmark = pytest.mark.gpu
 KAPPA = 0.141139
@@ -81,6 +82,10 @@ def test_mixed_solvers_on_the_pair_kernel(gpu, orc, L):
         it, outer, rr = lq.solve_mixed_DinvX_(sol, A, b, return_info=True)
         assert lat.get_param("pair32_active") == pair
         assert rr < 1e-18 and rel_err(sol.download(), xo) < 1e-8, (pair, it, outer, rr)
+        no_handoff(lat, "mixed CG pair %d" % pair)
+        assert lat.get_param("f32_form_active") == (3 if pair else 1)
+        steps = planned_steps(1e-18, float(np.vdot(psi, psi).real))
+        assert steps <= outer <= steps + 1, (pair, outer, steps)
         r = b.similar()
         lq.mul_(r, A, sol)
         lq.add_fermion_(r, -1.0, b)
@@ -90,6 +95,7 @@ def test_mixed_solvers_on_the_pair_kernel(gpu, orc, L):
     sig = [0.01, 0.1, 1.0]
     xs = [b.similar() for _ in sig]
     lq.shiftedcg_mixed(xs, sig, None, A, b, eps=1e-16)
+    no_handoff(lat, "mixed multi-shift on the pair kernel")
     for s, xj in zip(sig, xs):
         r = b.similar()
         lq.mul_(r, A, xj)
@@ -113,6 +119,8 @@ def test_pair32_is_not_used_where_it_does_not_apply(gpu, orc):
         sol = b.similar()
         it, outer, rr = lq.solve_mixed_DinvX_(sol, lq.DdagD_operator(D), b, return_info=True)
         assert lat.get_param("pair32_active") == 0, (L, extra)
+        no_handoff(lat, "%s %s" % (L, extra))
+        assert lat.get_param("f32_form_active") == (0 if "r" in extra else 1), (L, extra)      # general r: the site-per-lane kernel; everything else here: direction-split
         r = b.similar()
         lq.mul_(r, lq.DdagD_operator(D), sol)
         lq.add_fermion_(r, -1.0, b)
@@ -135,6 +143,7 @@ def test_x_update_in_the_epilogue_of_the_update_mode_kernel_gives_identical_solu
         x = b.similar()
         info = lq.solve_mixed_DinvX_(x, A, b, return_info=True)
         assert lat.get_param("pair32_active") == 1
+        no_handoff(lat, "mixed_xfuse %d" % fuse)
         out.append((info, x.download()))
     lat.set_param("mixed_xfuse", 0)
     assert out[0][0][:2] == out[1][0][:2] and out[0][0][2] < 1e-18
