@@ -585,6 +585,10 @@ int lqcd_bench_stencil_epilogue(lqcd_op_t op, lqcd_spinor_t dst, lqcd_spinor_t s
 int lqcd_bench_stencil_f32(lqcd_op_t op, lqcd_spinor_t dst, lqcd_spinor_t src, lqcd_spinor_t in, lqcd_spinor_t z, lqcd_spinor_t z2, int dagger, int mode, double coef,
                            int done, int conj, int soa, double* sums);
 
+/* the one-block final reduction behind every solver scalar on host partials ([block][value], soa != 0: [value][block]); guard[2] = the two slots behind out, set to the sentinel before the call.  No Julia binding (test aid) */
+#define LQCD_BENCH_REDUCE_SENTINEL (-1.2345e300)
+int lqcd_bench_reduce_partials(lqcd_ctx_t ctx, const double* host_partials, int nblocks, int nvals, int soa, double* out /* [nvals] */, double* guard /* [2] */);
+
 /* CG session for externally timed windows (bench.py brackets these with its own barriers/clock):
  * begin = r = b - D^+D x, p = r; iterate = enqueue n iterations (exit test disabled) and wait; end = release scratch */
 int lqcd_cg_session_begin(lqcd_op_t op, lqcd_spinor_t x, lqcd_spinor_t b);

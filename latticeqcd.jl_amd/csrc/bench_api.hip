@@ -230,6 +230,47 @@ extern "C" int lqcd_bench_stencil_f32(lqcd_op_t op, lqcd_spinor_t dst, lqcd_spin
     return mixed_bench_stencil_f32(op, dst, src, in, z, z2, dagger, mode, coef, done, conj, soa, sums);
 }
 
+// the one-block final reduction (blas.hip reduce_final behind reduce_to_slot, single rank, no scalar step) on partials the caller supplies (tests): a device buffer of
+// its own holds them (d_partial is too small for the large counts) with 64 NaNs behind them, so a read past the last partial poisons its sum instead of leaving the
+// buffer; out = d_scal[S_RED0 .. S_RED0 + nvals).  guard = the two slots behind the sums, which the call must not write: they are set to LQCD_BENCH_REDUCE_SENTINEL
+// before the launch, read back after it and then restored.
+extern "C" int lqcd_bench_reduce_partials(lqcd_ctx_t c, const double* host_partials, int nblocks, int nvals, int soa, double* out, double* guard) {
+    ARGCHK(c && host_partials && out && guard, "lqcd_bench_reduce_partials: null argument");
+    ARGCHK(nvals >= 1 && nvals <= PEER_RED_VALS && nblocks >= 1, "lqcd_bench_reduce_partials: one to eight values per block, at least one block");
+    static_assert(S_RED0 + PEER_RED_VALS + 2 <= SCAL_DOUBLES, "lqcd_bench_reduce_partials: guard slots");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t n = (size_t)nblocks * nvals;
+    double* buf = nullptr;
+    constexpr int TAIL = 64;
+    HIPCHK(hipMalloc((void**)&buf, (n + TAIL) * sizeof(double)));
+    double* const g = c->d_scal + S_RED0 + nvals;
+    const double sentinel[2] = {LQCD_BENCH_REDUCE_SENTINEL, LQCD_BENCH_REDUCE_SENTINEL};
+    double keep[2] = {0, 0}, res[PEER_RED_VALS + 2], tail[TAIL];
+    for (double& t : tail) t = std::nan("");
+    int st = LQCD_OK;
+    auto hip = [&](hipError_t e, const char* what) { if (e != hipSuccess && st == LQCD_OK) st = hip_fail(e, what, __FILE__, __LINE__); return st == LQCD_OK; };
+    bool armed = false;
+    if (hip(hipMemcpyAsync(buf, host_partials, n * sizeof(double), hipMemcpyHostToDevice, c->stream), "H2D partials") &&
+        hip(hipMemcpyAsync(buf + n, tail, sizeof tail, hipMemcpyHostToDevice, c->stream), "H2D tail") &&
+        hip(hipMemcpyAsync(keep, g, sizeof keep, hipMemcpyDeviceToHost, c->stream), "D2H guard slots") && hip(hipStreamSynchronize(c->stream), "sync") &&
+        hip(hipMemcpyAsync(g, sentinel, sizeof sentinel, hipMemcpyHostToDevice, c->stream), "H2D sentinel")) {
+        armed = true;
+        st = reduce_to_slot(c, nblocks, nvals, S_RED0, /*allreduce*/ false, 0, buf, soa != 0);
+        if (st == LQCD_OK) hip(hipMemcpyAsync(res, c->d_scal + S_RED0, (nvals + 2) * sizeof(double), hipMemcpyDeviceToHost, c->stream), "D2H sums");
+    }
+    if (armed) {      // the slots get their values back whatever happened in between
+        const hipError_t e = hipMemcpyAsync(g, keep, sizeof keep, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess && st == LQCD_OK) st = hip_fail(e, "H2D guard slots", __FILE__, __LINE__);
+    }
+    { const hipError_t e = hipStreamSynchronize(c->stream); if (e != hipSuccess && st == LQCD_OK) st = hip_fail(e, "sync", __FILE__, __LINE__); }
+    (void)hipFree(buf);
+    if (st != LQCD_OK) return st;
+    for (int v = 0; v < nvals; v++) out[v] = res[v];
+    guard[0] = res[nvals];
+    guard[1] = res[nvals + 1];
+    return LQCD_OK;
+}
+
 // CG session (externally timed windows); the state lives in the context, one open session per context
 namespace lqcd {
 struct CgSession { lqcd_op_s* op = nullptr; lqcd_spinor_s* x = nullptr; CgWork w; };

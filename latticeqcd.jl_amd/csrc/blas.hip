@@ -102,7 +102,8 @@ __global__ __launch_bounds__(FB) void reduce_final(const double* __restrict__ pa
     if (op && threadIdx.x == 0) cg_scalar_step(scal, op);
 }
 
-__global__ __launch_bounds__(RB) void axpy_kernel(double ar, double ai, const double2* __restrict__ x, double2* __restrict__ y, size_t n) {
+// x and y carry no __restrict__ here and in axpby_kernel: lqcd_axpy(a, x, x) and lqcd_axpby(a, x, b, x) are admitted (same_shape), y = (1 + a) x and (a + b) x
+__global__ __launch_bounds__(RB) void axpy_kernel(double ar, double ai, const double2* x, double2* y, size_t n) {
     for (size_t i = (size_t)blockIdx.x * RB + threadIdx.x; i < n; i += (size_t)gridDim.x * RB) {
         const double2 xv = x[i];
         double2 yv = y[i];
@@ -112,8 +113,7 @@ __global__ __launch_bounds__(RB) void axpy_kernel(double ar, double ai, const do
     }
 }
 
-__global__ __launch_bounds__(RB) void axpby_kernel(double ar, double ai, const double2* __restrict__ x, double br, double bi,
-                                                   double2* __restrict__ y, size_t n) {
+__global__ __launch_bounds__(RB) void axpby_kernel(double ar, double ai, const double2* x, double br, double bi, double2* y, size_t n) {
     for (size_t i = (size_t)blockIdx.x * RB + threadIdx.x; i < n; i += (size_t)gridDim.x * RB) {
         const double2 xv = x[i], yv = y[i];
         double2 r;

@@ -54,6 +54,46 @@ def test_md_kernels_match_oracle(gpu, orc, L):
         lq.gauge_force_(U, U, BETA)
 
 
+def integer_momenta(shape, seed):
+    """traceless anti-Hermitian matrices with integer parts in [-7, 7] on every link: z above the diagonal, -conj(z) in the transposed position, i (p, q, -p - q) on it"""
+    rng = np.random.default_rng(seed)
+    re, im = np.zeros(shape, dtype=np.int64), np.zeros(shape, dtype=np.int64)
+    for a, b in ((0, 1), (0, 2), (1, 2)):
+        zr, zi = rng.integers(-7, 8, size=shape[:-2]), rng.integers(-7, 8, size=shape[:-2])
+        re[..., a, b], im[..., a, b] = zr, zi
+        re[..., b, a], im[..., b, a] = -zr, zi
+    p = rng.integers(-7, 8, size=shape[:-2])
+    q = rng.integers(np.maximum(-7, -7 - p), np.minimum(7, 7 - p) + 1)
+    im[..., 0, 0], im[..., 1, 1], im[..., 2, 2] = p, q, -p - q
+    assert np.abs(re).max() <= 7 and np.abs(im).max() <= 7 and (im[..., 2, 2] != 0).any() and not np.trace(im, axis1=-2, axis2=-1).any()
+    return re, im
+
+
+@pytest.mark.parametrize("L", [(6, 6, 4, 2), (8, 4, 6, 2), (16, 16, 16, 32)])
+def test_momentum_action_is_exact_on_integer_momenta(gpu, L):
+    """lqcd_momentum_action is K = -sum tr P^2 (csrc/md.hip; the header's p.p/2 with the reference's p.p = -2 sum tr P^2: no further factor), its block partials
+    go through the shared final reduction with nb = link_grid = 2 nch workgroups, nch = ceil(Vh / 64) chunks of 64 sites per parity (csrc/gauge_staple.h link_grid,
+    link_of_thread; the library does not expose nch, so it is computed here from that chunk size).  On integer matrices every product, partial and total is an
+    exact integer, so a link that is dropped or counted twice moves K by at least 1.  (6,6,4,2): Vh = 144, the third chunk of a parity holds 16 sites;
+    16.16.16.32: 2048 workgroups, the large form of the reduction."""
+    lq = gpu
+    lat = lq.Lattice(L)
+    Vh = L[0] * L[1] * L[2] * L[3] // 2
+    nb = 2 * ((Vh + 63) // 64)
+    if L == (16, 16, 16, 32):
+        assert 2 * Vh // 64 > 1024 and nb > 1024
+    if L == (6, 6, 4, 2):
+        assert Vh % 64 == 16
+    re, im = integer_momenta(lat.gauge_shape, 900 + L[0] + L[3])
+    # -Re tr P^2 = -sum_ab Re(P_ab P_ba) in integers (what the kernel forms, whatever the symmetry of P)
+    want = -int((re * np.swapaxes(re, -1, -2) - im * np.swapaxes(im, -1, -2)).sum())
+    assert want == int((re * re + im * im).sum()) and 0 < want < 2 ** 53
+    P = lq.Gaugefields(lat).upload(re + 1j * im)
+    K = lq.momentum_action(P)
+    assert K == float(want), (L, nb, K, want)
+    assert lq.momentum_action(P) == K
+
+
 def test_momentum_sampling(gpu, orc):
     lq = gpu
     L = (8, 8, 8, 8)
