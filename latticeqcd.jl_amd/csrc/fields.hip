@@ -817,6 +817,7 @@ int gauge_ensure_tgauge(lqcd_gauge_s* g, bool want8) {
     if (g->version12t == g->version && g->data12t && g->gfix) return (want8 && !(g->tgauge8_built && g->version8t == g->version)) ? gauge_build_tgauge8(g) : LQCD_OK;
     lqcd_ctx_s* c = g->ctx;
     g->tgauge_ok = false;
+    g->tgauge8_built = false; g->tgauge8_dev = 1e300;      // no copy of this version (yet): the deviation of the previous one is not this field's
     if (!g->recon_ok || c->geom.part[0] || c->geom.part[1] || c->geom.part[2] || c->geom.part[3] || c->geom.L[3] < 2) return LQCD_OK;
     HIPCHK(hipSetDevice(c->device));
     if (!g->data12t) HIPCHK(hipMalloc((void**)&g->data12t, gauge12_elems(c->geom) * sizeof(double2)));
@@ -835,8 +836,6 @@ int gauge_ensure_tgauge(lqcd_gauge_s* g, bool want8) {
     g->tgauge_ok = dev <= 1e-14;
     g->tgauge_dev = dev;
     g->version12t = g->version;
-    g->tgauge8_built = false;
-    g->tgauge8_dev = 1e300;
     return want8 ? gauge_build_tgauge8(g) : LQCD_OK;
 }
 
