@@ -130,6 +130,9 @@ int lqcd_ctx_sync(lqcd_ctx_t ctx);
  * eligible launch take it),
  * nt_centre (1 [default]: the update source of the scalar-addressing Wilson kernel's update and recurrence modes -- read once per launch at the centre, never a neighbour -- is a
  * non-temporal load and stays out of the L2; a hint, identical bits; 0: plain load),
+ * nt_active (read-only: the cache hints of the last stencil launch, -1 before the first.  Bits 0-3: the hint word the kernel was given -- 1 / 2 streamed backward / forward
+ * link loads, 4 streamed output stores, 8 streamed spinor loads of the site-per-lane kernels; bit 4: the launched instance was one with the streamed backward-link loads
+ * compiled in, which the 12 + delta, five-dimensional, multi-column and site-per-lane launches never are),
  * halo_fold (1 [default], round 5: where the collective timing picks the one-stream halo schedule 3, the stencil launch takes the boundary hops from the ghost
  * buffers itself -- no exterior kernel, for every operator and both precisions; read-only halo_fold_active), cg_persist (1 [default]: a staggered CG on an unpartitioned lattice of
  * at most 256 chunks of 64 sites runs as ONE launch -- initial residual and all iterations, two grid-wide synchronisations per iteration, every wait bounded: if the workgroups are not all resident (a busy GPU) x is left untouched, the solve is

@@ -356,6 +356,7 @@ static int* param_ptr(lqcd_ctx_s* c, const char* key) {
     if (!strcmp(key, "dslash_yshare")) return &c->tun.dslash_yshare;
     if (!strcmp(key, "yshare_active")) return &c->tun.yshare_active;
     if (!strcmp(key, "nt_centre")) return &c->tun.nt_centre;
+    if (!strcmp(key, "nt_active")) return &c->tun.nt_active;
     if (!strcmp(key, "cg_persist")) return &c->tun.cg_persist;
     if (!strcmp(key, "md_remap")) return &c->tun.md_remap;
     if (!strcmp(key, "staple_recon")) return &c->tun.staple_recon;

@@ -641,6 +641,9 @@ struct Tunables {
     int yshare_active = 0;    // read-only: 1 if the last eligible launch of the scalar-addressing kernel took the y-share
     int nt_centre = 1;        // scalar-addressing Wilson kernel, update and recurrence modes: the update source (read once per launch at the centre) is a non-temporal load: it
                               // stays out of the L2 the neighbour spinors and links of a tile live in.  A hint; CG +0.7 % at steady clocks (profiles/r15_xshare_ab.log)
+    int nt_active = -1;       // read-only: the cache hints of the last stencil launch (launch_stencil_interior, launch_pair32_interior, mrhs_hop_launch); -1 none yet.  Bits 0-3: the
+                              // kernel's runtime hint word (KArgs::nt: 1 / 2 backward / forward link loads, 4 output stores, 8 the site-per-lane kernels' spinor loads), bit 4: the
+                              // launched instance was an NTB = true one (streamed backward-link loads compiled in).  Tests use it to tell that they reached the instance they mean
     int cg_skip_done = 1;     // fused CG: the first Dslash of an iteration checks the convergence flag as well (0: only the second does)
     int clover_transport = 0; // 1: build the clover sums by the plaquette-transport passes also on an unpartitioned lattice (tests)
     int stag_both = 0;            // 1: staggered split kernel issues the loads of both hops of a direction back to back (unpartitioned lattices)

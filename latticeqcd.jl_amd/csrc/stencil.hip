@@ -1970,6 +1970,7 @@ static bool use_dirsplit(lqcd_ctx_s* c, int kind, real r) {   // variants 1/2/3 
 template <int TB>
 static int launch_interior_tb(lqcd_ctx_s* c, const StencilCall& s) {
     KArgs k = make_kargs(c, s, TB);
+    c->tun.nt_active = k.nt & 15;      // (the site-per-lane kernels read every hint at run time: no NTB instance)
     dim3 grid(k.nblocks), block(TB);
     const size_t pad = (size_t)c->tun.lds_pad_kb * 1024;  // occupancy limiter (experiments)
     if (s.kind == LQCD_WILSON) {
@@ -2167,6 +2168,7 @@ int launch_stencil_interior(lqcd_ctx_s* c, const StencilCall& s) {
     }
     if (use_dirsplit(c, s.kind, s.r)) {
         KArgs k = make_kargs(c, s, 64);
+        c->tun.nt_active = k.nt & 15;      // read-only key: the hint word of this launch; bit 4 is added where an NTB = true instance is chosen below
         const size_t pad = (size_t)c->tun.lds_pad_kb * 1024;
         // "12 + delta" links are read by the scalar-addressing Wilson kernel alone: every other launch takes the 18 stored reals
         const bool delta = s.gauge12_delta && !kF32Build && s.kind == LQCD_WILSON && k.gauge12 && !k.alpha_partials && !k.dot_partial && !s.clover_on_hop && !k.clover && !s.fold &&
@@ -2183,6 +2185,7 @@ int launch_stencil_interior(lqcd_ctx_s* c, const StencilCall& s) {
             const dim3 sg(k.nblocks), sb_(256);
             if (both) {
                 const bool ntb = (k.nt & 1) != 0;
+                if (ntb) c->tun.nt_active |= 16;
                 if (k.gauge12) { if (ntb) hipLaunchKernelGGL((staggered_dirsplit<true, true, true>), sg, sb_, pad, c->stream, k);
                                  else hipLaunchKernelGGL((staggered_dirsplit<true, true, false>), sg, sb_, pad, c->stream, k); }
                 else { if (ntb) hipLaunchKernelGGL((staggered_dirsplit<false, true, true>), sg, sb_, pad, c->stream, k);
@@ -2199,6 +2202,7 @@ int launch_stencil_interior(lqcd_ctx_s* c, const StencilCall& s) {
                 // round 6: the scalar-addressing kernel with the inverse blocks in its epilogue (CINV instance)
                 PipeArgs a = make_pipe_args(c, k, s);
                 const bool ntb = (k.nt & 1) != 0;
+                if (ntb) c->tun.nt_active |= 16;
                 if (s.dagger) { if (ntb) hipLaunchKernelGGL((wilson_dirsplit_s<true, true, true, true, false, false, false, true>), grid, block, 0, c->stream, a);
                                 else hipLaunchKernelGGL((wilson_dirsplit_s<true, true, false, true, false, false, false, true>), grid, block, 0, c->stream, a); }
                 else { if (ntb) hipLaunchKernelGGL((wilson_dirsplit_s<false, true, true, true, false, false, false, true>), grid, block, 0, c->stream, a);
@@ -2217,6 +2221,7 @@ int launch_stencil_interior(lqcd_ctx_s* c, const StencilCall& s) {
             else if (k.gauge12 && c->tun.dslash_pipe == 2 && wilson_pipe_applies(c, s.kind, s.r, s.parity_mode, false)) {      // the scalar-addressing form
                 PipeArgs a = make_pipe_args(c, k, s);
                 const bool ntb = (k.nt & 1) != 0;
+                if (ntb) c->tun.nt_active |= 16;
                 if (s.dagger) { if (ntb) hipLaunchKernelGGL((wilson_dirsplit_s<true, true, true, true>), grid, block, 0, c->stream, a);
                                 else hipLaunchKernelGGL((wilson_dirsplit_s<true, true, false, true>), grid, block, 0, c->stream, a); }
                 else { if (ntb) hipLaunchKernelGGL((wilson_dirsplit_s<false, true, true, true>), grid, block, 0, c->stream, a);
@@ -2240,6 +2245,7 @@ int launch_stencil_interior(lqcd_ctx_s* c, const StencilCall& s) {
             if (k.gauge12 && c->tun.clover_hop_s && c->tun.dslash_pipe == 2 && !k.alpha_partials && !s.fold && wilson_pipe_applies(c, s.kind, s.r, s.parity_mode, false)) {
                 PipeArgs a = make_pipe_args(c, k, s);      // round 6: the scalar-addressing kernel, inverse blocks in its epilogue
                 const bool ntb = (k.nt & 1) != 0;
+                if (ntb) c->tun.nt_active |= 16;
                 if (s.dagger) { if (ntb) hipLaunchKernelGGL((wilson_dirsplit_s<true, true, true, false, false, false, false, true>), grid, block, 0, c->stream, a);
                                 else hipLaunchKernelGGL((wilson_dirsplit_s<true, true, false, false, false, false, false, true>), grid, block, 0, c->stream, a); }
                 else { if (ntb) hipLaunchKernelGGL((wilson_dirsplit_s<false, true, true, false, false, false, false, true>), grid, block, 0, c->stream, a);
@@ -2260,6 +2266,7 @@ int launch_stencil_interior(lqcd_ctx_s* c, const StencilCall& s) {
             if (c->tun.dslash_pipe == 3) { a.ctr = nullptr; a.per_wg = wilson_pipe_per_wg(c, k.nblocks); }
             const dim3 pg(c->tun.dslash_pipe == 1 ? wilson_pipe_grid(c, k.nblocks, s.prec) : c->tun.dslash_pipe == 3 ? k.nblocks / a.per_wg : k.nblocks), pb(256);
             const bool ntb = (k.nt & 1) != 0;
+            if (ntb && s.dw_ls <= 1 && !delta) c->tun.nt_active |= 16;      // (the five-dimensional and 12 + delta launches below have no NTB = true instance)
             pipe_sweep_args(c, k, s, delta, a);      // (read by the launches of the last branch below only)
             pipe_xshare_args(c, k, s, delta, a);     // (the 12 + delta launch and the last branch)
 #ifndef LQCD_F32

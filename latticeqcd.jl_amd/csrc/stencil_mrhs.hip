@@ -220,6 +220,7 @@ int mrhs_hop_launch(lqcd_op_s* op, const MrhsCall& s) {
     k.remap = bm.remap; k.cps = bm.cps; k.cpp = bm.cpp; k.ysplit = bm.ysplit; k.cpr = bm.cpr; k.ty = bm.ty; k.tz = bm.tz; k.nsub = 0;
     k.d_perpass = bm.d_perpass; k.d_cpr = bm.d_cpr; k.d_ysplit = bm.d_ysplit; k.d_ty = bm.d_ty;
     k.nt = c->tun.nt_store ? 4 : 0;
+    c->tun.nt_active = k.nt;      // read-only key: plain link loads, no NTB instance
     const dim3 grid(k.nblocks);
     for (int j0 = 0; j0 < s.n; j0 += MR_NB) {
         const int nb = std::min(MR_NB, s.n - j0);

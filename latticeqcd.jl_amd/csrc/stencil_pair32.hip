@@ -597,6 +597,7 @@ int launch_pair32_interior(lqcd_ctx_s* c, const StencilCall& s) {
     a.d_ty = make_fastdiv(std::max(1, a.ty)); a.d_cpp = make_fastdiv(std::max(1, a.cpp));
     const dim3 grid(s.parity_mode == 2 ? pair32_num_blocks(c) : pair32_num_blocks(c) / 2), block(256);
     const bool ntb = (c->tun.nt_gauge & 1) != 0;
+    c->tun.nt_active = (ntb ? 17 : 0) | (a.nt_store ? 4 : 0);      // read-only key, in the bits of stencil.hip: backward-link loads (bit 0, an NTB instance: bit 4), output stores (bit 2)
     auto go = [&](auto dag, auto nt, auto dot, auto h16) {
         hipLaunchKernelGGL((wilson_dirsplit_pair32<decltype(dag)::value, decltype(nt)::value, decltype(dot)::value, decltype(h16)::value>), grid, block, 0, c->stream, a);
     };

@@ -2,7 +2,8 @@
 D forwards, D^+ backwards).  A reversed launch gives every workgroup another virtual block of the same map -- same sites, same operations, partials indexed by virtual
 block -- so everything here is compared bit for bit with the forward launch of the same library.
 Shapes: 16.8.8.4 (one pass, no y split, 64 workgroups, seam slices are half the lattice), 16.16.16.8 with xcd_nsub = 16, xcd_ysplit = 2 (two passes and (y,z) tiles,
-512 workgroups: the map structure of 32^3 x 64 at the smallest size that has it), 16.16.16.32 with default settings (2048 workgroups)."""
+512 workgroups: two passes like 32^3 x 64, but split 2 with ty = 1 -- the map 32^3 x 64 resolves to, split 4 with ty = 2, runs on 32.32.8.4 in
+tests/test_gpu_fullsize_hints.py), 16.16.16.32 with default settings (2048 workgroups)."""
 import numpy as np
 import pytest
 

@@ -3,7 +3,7 @@ x-neighbours from one load of the opposite-parity chunk and a lane shift through
 everything here is compared bit for bit with the two-load path of the same library, and with the oracle at the bound of the operator tests (1e-13).  The streaming
 hint on the centre read of the update source (tunable nt_centre) is checked the same way.
 Shapes: the smallest the scalar-addressing kernel takes with XH = 16 -- 32.4.8.4 (one chunk per z-plane), 32.8.8.4 (two), 32.16.16.8 with xcd_nsub = 16,
-xcd_ysplit = 2 (the two-pass tile map of 32^3 x 64, 1024 workgroups) -- and 16.8.8.4 (XH = 8), where the gate must decline.
+xcd_ysplit = 2 (a two-pass tile map, split 2, 1024 workgroups; 32^3 x 64 itself resolves to split 4, which tests/test_gpu_fullsize_hints.py runs on 32.32.8.4) -- and 16.8.8.4 (XH = 8), where the gate must decline.
 The bit-equality of whole solves on an ill-conditioned system (32.4.8.4, 1793 iterations): tests/test_gpu_hard_solves.py."""
 import numpy as np
 import pytest

@@ -3,7 +3,7 @@ of 4 the y wave takes the in-chunk y-neighbours -- rows 0-2 forwards, rows 1-3 b
 loads only row 3's forward and row 0's backward neighbour itself.  Projection and sign stay on the receiving lane, so everything here is compared bit for bit with
 dslash_yshare = 0 of the same library, and with the oracle at the bound of the operator tests (1e-13).
 Shapes: the smallest at which each edge case exists -- 32.4.8.4 (one chunk per z-plane: both edge rows wrap into the lane's own chunk), 32.8.8.4 (two chunks: one interior
-chunk boundary), 32.12.8.4 (three chunks, L1 no power of two), 32.16.16.8 with xcd_nsub = 16, xcd_ysplit = 2 (the two-pass tile map of 32^3 x 64) -- and 16.8.8.4 (XH = 8),
+chunk boundary), 32.12.8.4 (three chunks, L1 no power of two), 32.16.16.8 with xcd_nsub = 16, xcd_ysplit = 2 (a two-pass tile map, split 2; 32^3 x 64 itself resolves to split 4, which tests/test_gpu_fullsize_hints.py runs on 32.32.8.4) -- and 16.8.8.4 (XH = 8),
 where the gate must decline.  The lane map: tests/test_cpu_yshare_map.py."""
 import numpy as np
 import pytest
