@@ -164,7 +164,7 @@ int lqcd_ctx_sync(lqcd_ctx_t ctx);
  * stopping test waits for the summed value); 0 the generic chain; 3 is refused (a grid-barrier form of 4, measured slower and removed); read-only bicg_xrp_active: 0 | 2 (form 4)), action_eo_solver (1 [default]: lqcd_fermi_action / lqcd_calc_UdSfdU / lqcd_action_* solve the Wilson(-clover) normal
  * equations as two even-odd BiCGStab solves under the reference's stopping rule; 0: CG), bicg_mixed (1: lqcd_solve_bicgstab_eo on the plain Wilson operator runs an fp32 inner
  * chain inside an fp64 defect correction, the stopping rule holds for the true fp64 residual; mixed_action_solver = 1 switches it on for the action solves), lazy_links (1: the per-direction link-call triples are recorded and fused -- the temporaries of a completed triple are then never written, so the C ABI's default is 0 (eager) and the Julia / Python bindings switch it on when they create a context,
- * see lqcd_link_*; read-only lazy_open, lazy_deferred; a recorded update runs under the settings in force when it was ASKED for: lqcd_ctx_set_param with a value that
+ * see lqcd_link_*; read-only lazy_open, lazy_deferred, peer_reductions (peer-mapped backend: the reductions this rank has issued; equal on every rank or a wait times out); a recorded update runs under the settings in force when it was ASKED for: lqcd_ctx_set_param with a value that
  * differs from the current one runs what is recorded first), lazy_merge (1 [default]: a complete link update U <- exp(a P) U waits unlaunched and a second one of the same
  * fields, with nothing in between that reads U or writes P, adds its step -- the back-to-back half steps of runMD_QPQ_sw!, standardMD.jl:146-166);
  * several right-hand sides: mrhs_active (read-only: columns per stencil launch of the last lqcd_*_multi call, 0 if it looped over the single-column entries), meson_mrhs (1: the meson

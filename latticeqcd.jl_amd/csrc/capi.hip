@@ -456,6 +456,7 @@ extern "C" int lqcd_ctx_get_param(lqcd_ctx_t c, const char* key, int* value) {
         *value = (int)c->parked_gauges.size();
         return LQCD_OK;
     }
+    if (!strcmp(key, "peer_reductions")) { *value = (int)(c->peer.red_seq & 0x7fffffff); return LQCD_OK; }      // peer backend: reductions issued so far by THIS rank (comm_red_args); every rank must report the same count
     if (!strcmp(key, "lazy_open")) { *value = c->lazy.kind; return LQCD_OK; }
     if (!strcmp(key, "lazy_deferred")) { *value = (int)c->lazy.done.size() + (c->lazy.has_pend ? 4 : 0) + (c->lazy.has_pp ? 4 : 0); return LQCD_OK; }
     int* p = param_ptr(c, key);
